@@ -5,8 +5,14 @@ One step = one pass of the classify kernel over one batch of synthetic 5-tuples 
 resident in HBM (BASELINE.json configs[1] by default: 1k-rule gen-policy-shaped table,
 64M tuples per GPU). Multi-GPU (torchrun, one process per GPU): every rank classifies its
 own shard (tuple index range) against replicated tables -- no data-path collective, weak
-scaling. After the timed region the per-rule hit counters are summed across ranks with one
-RCCL all-reduce (the statscollector path) and its time is reported separately.
+scaling.
+
+A plain run sets up, warms up, times --steps steps, writes the last step's outputs when
+--dump-outputs is given, and prints the line. With --full it goes on, after the timed region,
+to everything reported beside `value`: the steady-state launches, the measured stream
+ceiling, the per-rank oracle self-check, the CPU baselines, the side configs, and under
+torchrun the per-rule hit counters summed across ranks with one RCCL all-reduce (the
+statscollector path), its time reported separately.
 
 Prints ONE JSON line (rank 0). See DESIGN.md §Measurement for the byte accounting.
 """
@@ -31,6 +37,7 @@ from vpp_amd import workloads as W  # noqa: E402
 METRIC = "classified 5-tuples/sec (Mpps) at 1/2/4/8 GPUs vs rule count; % of HBM peak"
 HBM_PEAK_GBS = 8000.0           # MI355X HBM3E spec (MI355X_MICROARCH.md)
 MODE_NAME = {0: "single", 1: "perpod", 2: "conn"}
+DUMP_MAX = 1 << 21              # --dump-outputs: verdicts written per rank (float64 beside float64 indices: 32 MiB)
 
 
 def parse():
@@ -64,6 +71,17 @@ def parse():
     p.add_argument("--no-check", action="store_true", help="skip the per-rank oracle self-check")
     p.add_argument("--per-table", action="store_true",
                    help="PERPOD/CONN through the per-table blobs + IP hash instead of the node classifier")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run everything measured or checked beside `value`: the "
+                        "steady-state launches, the stream ceiling and device-copy probes, the per-rank oracle "
+                        "self-check, the RCCL counter all-reduce (torchrun launches), the CPU baselines and the "
+                        "side configs (--side, --no-cpu, --no-check, --check-tuples, --cpu-* and "
+                        "--faithful-seconds apply to these legs only). Without it a run sets up, warms up, "
+                        "times the steps and prints the line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last timed step computed as DIR/<name>.npy "
+                        "(float64): the verdicts -- all of them up to %d, a fixed seeded sample of a larger "
+                        "batch beside its indices -- and the hit counters when the run counts" % DUMP_MAX)
     p.add_argument("--cpu-dry-run", action="store_true",
                    help="no GPU: the launcher, sharding, timing and counter all-reduce over gloo, with the "
                         "product's per-tuple code run on the host (tests only; no throughput claim)")
@@ -161,12 +179,8 @@ def main():
     ms_per_step = wall * 1e3 / a.steps
     total_tuples = VD.sum_over_ranks(n, "cuda") * a.steps
     mpps = total_tuples / wall / 1e6
-
-    # after the timed region (reported beside `value`, never as it): the same launches once the
-    # core clock has settled -- the first ~40 launches of a burst run at a lower clock while the
-    # chip's power management settles (profiles/r03_ramp_*: config 3 launches 4-10 at 1.8-1.95
-    # GHz, 2.37 GHz from launch ~36), which the driver's 5-warm-up / 20-step window catches
-    steady = steady_state(e, w, b, out, cptr, n, world)
+    if a.dump_outputs:  # before any later leg launches into `out` or the counters again
+        dump_outputs(a.dump_outputs, out, cptr, rank, world)
 
     bpt, fields = bytes_per_tuple(w)
     achieved = n * bpt / (kern_ms * 1e-3) / 1e9
@@ -186,7 +200,32 @@ def main():
                      "bytes_per_tuple": bpt, "fields": fields, "kernel_ms": round(kern_ms, 4),
                      "algorithmic_bytes_per_launch": n * bpt, "traffic_source": traffic_src},
     }
-    line["steady_state"] = steady
+    side = a.side if a.side != "auto" else ("3,4,5" if a.config == 2 and not a.rules and not a.counters and
+                                             not a.tuples and not a.per_table else "none")
+    if a.full:
+        full_legs(a, line, w, b, out, cptr, base, n, bpt, achieved, rank, world, launched)
+    if a.full and side != "none":
+        del b, out, counters, cptr
+        torch.cuda.empty_cache()
+        for c in side.split(","):
+            line["side_config%s" % c] = side_line(a, int(c), rank, world, local, launched,
+                                                  max(1, host_cores() // world))
+            torch.cuda.empty_cache()
+    if rank == 0:
+        print(json.dumps(line), file=json_out, flush=True)
+    if launched:
+        dist.destroy_process_group()
+
+
+def full_legs(a, line, w, b, out, cptr, base, n, bpt, achieved, rank, world, launched):
+    """--full: what a run of the main config measures and checks beside `value`, after the timed
+    region, added to the bench line."""
+    e = w.engine
+    # reported beside `value`, never as it: the same launches once the core clock has settled
+    # -- the first ~40 launches of a burst run at a lower clock while the chip's power
+    # management settles (profiles/r03_ramp_*: config 3 launches 4-10 at 1.8-1.95 GHz, 2.37 GHz
+    # from launch ~36), which the driver's 5-warm-up / 20-step window catches
+    line["steady_state"] = steady_state(e, w, b, out, cptr, n, world)
     # the same fraction against what moving this launch's own bytes reaches on this GPU (after
     # the timed region): pg_stream_probe issues the classify launch's loads and store over the
     # same batch without the classification; torch's 1 GiB device copy beside it
@@ -216,18 +255,6 @@ def main():
         line["parity_per_rank"] = pars
     if rank == 0 and world == 1 and not a.no_cpu:
         line["cpu_baseline"] = cpu_baseline(w, b, out, a.cpu_sample, a.faithful_seconds, a.cpu_seconds)
-    side = a.side if a.side != "auto" else ("3,4,5" if a.config == 2 and not a.rules and not a.counters and
-                                             not a.tuples and not a.per_table else "none")
-    if side != "none":
-        del b, out, counters
-        torch.cuda.empty_cache()
-        for c in side.split(","):
-            line["side_config%s" % c] = side_line(a, int(c), rank, world, local, launched, check_threads)
-            torch.cuda.empty_cache()
-    if rank == 0:
-        print(json.dumps(line), file=json_out, flush=True)
-    if launched:
-        dist.destroy_process_group()
 
 
 def side_line(a, config, rank, world, local, launched, check_threads):
@@ -280,6 +307,29 @@ def side_line(a, config, rank, world, local, launched, check_threads):
                                 "counters_equal_oracle_histogram": all(p["counters_equal_oracle_histogram"]
                                                                        for p in pars)}
     return res
+
+
+def dump_outputs(path, out, cptr, rank, world):
+    """--dump-outputs: what the last timed step left in the caller's buffers, as float64 .npy
+    files under `path` (a u32 verdict word -- action << 30 | rule slot -- is exact in float64).
+    verdicts.npy holds the whole verdict array up to DUMP_MAX tuples; of a larger one the
+    tuples at DUMP_MAX sorted indices drawn by a fixed-seed generator (a function of the batch
+    size alone, so two runs with the same arguments write the same tuples), the indices beside
+    them in verdict_index.npy. counters.npy, when the run counts: the per-rule hit counters the
+    caller's tensor holds after the last step (they add up over the warm-up and timed steps).
+    Ranks of a multi-GPU run write their own shard's files, suffixed _rank<r>."""
+    os.makedirs(path, exist_ok=True)
+    sfx = "_rank%d" % rank if world > 1 else ""
+    n = out.numel()
+    if n > DUMP_MAX:
+        idx = np.sort(np.random.default_rng(0x5eed).integers(0, n, DUMP_MAX, dtype=np.int64))
+        got = out[torch.from_numpy(idx).to(out.device)].cpu().numpy()
+        np.save(os.path.join(path, "verdict_index%s.npy" % sfx), idx.astype(np.float64))
+    else:
+        got = out.cpu().numpy()
+    np.save(os.path.join(path, "verdicts%s.npy" % sfx), got.view(np.uint32).astype(np.float64))
+    if cptr is not None:
+        np.save(os.path.join(path, "counters%s.npy" % sfx), cptr.cpu().numpy().astype(np.float64))
 
 
 def steady_state(e, w, b, out, cptr, n, world, settle=60, timed=20):

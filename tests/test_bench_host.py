@@ -33,6 +33,45 @@ def _run(w, n):
     return bench.cpu_baseline(w, _Batch(tup), out, n, faithful_s=0.2, budget_s=0.4)
 
 
+def test_plain_run_is_the_default(monkeypatch):
+    """--full is off unless asked for; --dump-outputs takes a directory"""
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 3
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path):
+    """--dump-outputs: a batch up to DUMP_MAX is written whole, a larger one as the same sorted
+    sample on every call; float64 holds the u32 verdict word (action bits 30-31 set included) and
+    the i64 counters exactly; ranks of a multi-GPU run write their own files."""
+    rng = np.random.default_rng(7)
+    small = rng.integers(0, 1 << 32, 1001, dtype=np.uint64).astype(np.uint32)
+    cnt = torch.arange(5, dtype=torch.int64) << 40
+    bench.dump_outputs(str(tmp_path / "a"), torch.from_numpy(small.view(np.int32)), cnt, 0, 1)
+    v = np.load(tmp_path / "a" / "verdicts.npy")
+    assert v.dtype == np.float64 and np.array_equal(v, small.astype(np.float64)) and v.max() >= 2.0 ** 31
+    assert np.array_equal(np.load(tmp_path / "a" / "counters.npy"), cnt.numpy().astype(np.float64))
+    assert not (tmp_path / "a" / "verdict_index.npy").exists()
+
+    n = bench.DUMP_MAX + 4097
+    big = rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)
+    out = torch.from_numpy(big.view(np.int32))
+    bench.dump_outputs(str(tmp_path / "b"), out, None, 0, 1)
+    bench.dump_outputs(str(tmp_path / "c"), out, None, 1, 2)
+    idx = np.load(tmp_path / "b" / "verdict_index.npy")
+    v = np.load(tmp_path / "b" / "verdicts.npy")
+    assert idx.dtype == np.float64 and len(idx) == len(v) == bench.DUMP_MAX
+    assert (np.diff(idx) >= 0).all() and idx[0] >= 0 and idx[-1] < n
+    assert np.array_equal(v, big[idx.astype(np.int64)].astype(np.float64))
+    assert not (tmp_path / "b" / "counters.npy").exists()
+    assert np.array_equal(np.load(tmp_path / "c" / "verdict_index_rank1.npy"), idx)
+    assert np.array_equal(np.load(tmp_path / "c" / "verdicts_rank1.npy"), v)
+    assert v.nbytes + idx.nbytes <= 64 << 20
+
+
 def test_conn_baseline_uses_the_connection_endpoint_rules():
     """CONN (config 5's topology): remote pod <-> non-pod and non-pod <-> non-pod make no
     evaluation (aclengine_mock.go:343-347, 388-392) in the baseline too -- its sample and its

@@ -10,7 +10,7 @@ for c in $CONFIGS; do
     cc=${c%c}; A=""; case $c in *c) A="--counters";; esac
     A="$A --config ${cc%%r*}"; case $cc in *r*) A="$A --rules ${cc#*r}";; esac
     echo "[$(date +%T)] bench $A $*"
-    timeout -k 10 300 python bench.py $A "$@" > "$O/b$c.json" 2> "$O/b$c.err" || { tail -20 "$O/b$c.err"; exit 1; }
+    timeout -k 10 300 python bench.py --full $A "$@" > "$O/b$c.json" 2> "$O/b$c.err" || { tail -20 "$O/b$c.err"; exit 1; }
     python - "$O/b$c.json" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -29,7 +29,7 @@ for lib in $LIBS; do
       echo "[$(date +%T)] $lib config $c pass $i:$ok"
       VPP_AMD_LIB=$R/vpp_amd/$lib timeout -s KILL 120 rocprofv3 --pmc $ok --output-format csv \
           -d "$O/${lib%.so}/pmc_c${c}_p$i" -o run -- \
-          python3 "$R/bench.py" --config "${c%c}" $cnt --no-cpu --no-check --steps 3 --warmup 1 \
+          python3 "$R/bench.py" --full --config "${c%c}" $cnt --no-cpu --no-check --steps 3 --warmup 1 \
           > "$O/${lib%.so}/pmc_c${c}_p$i.log" 2>&1 || { tail -5 "$O/${lib%.so}/pmc_c${c}_p$i.log"; exit 1; }
     done
   done

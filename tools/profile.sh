@@ -24,17 +24,17 @@ PASSES=(
 for c in $CONFIGS; do
     A="--config ${c%%r*}"; case $c in *r*) A="$A --rules ${c#*r}";; esac
     step bench config $c
-    timeout -k 10 300 python3 "$R/bench.py" $A $EXTRA > "$O/bench_c$c.json" 2> "$O/bench_c$c.err" \
+    timeout -k 10 300 python3 "$R/bench.py" --full $A $EXTRA > "$O/bench_c$c.json" 2> "$O/bench_c$c.err" \
         || { tail -20 "$O/bench_c$c.err"; exit 1; }
     cut -c1-400 "$O/bench_c$c.json"
     step trace config $c
     timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_c$c" -o run -- \
-        python3 "$R/bench.py" $A --no-cpu --no-check $EXTRA > "$O/prof_c$c.log" 2>&1 \
+        python3 "$R/bench.py" --full $A --no-cpu --no-check $EXTRA > "$O/prof_c$c.log" 2>&1 \
         || { tail -20 "$O/prof_c$c.log"; exit 1; }
     for ctr in FETCH_SIZE WRITE_SIZE; do
         step pmc $ctr config $c
         timeout -s KILL 120 rocprofv3 --pmc $ctr --output-format csv -d "$O/pmc_${ctr}_c$c" -o run -- \
-            python3 "$R/bench.py" $A --no-cpu --no-check --steps 3 --warmup 1 $EXTRA > "$O/pmc_${ctr}_c$c.log" 2>&1 \
+            python3 "$R/bench.py" --full $A --no-cpu --no-check --steps 3 --warmup 1 $EXTRA > "$O/pmc_${ctr}_c$c.log" 2>&1 \
             || { tail -20 "$O/pmc_${ctr}_c$c.log"; exit 1; }
     done
     i=0
@@ -45,7 +45,7 @@ for c in $CONFIGS; do
         [ -n "$ok" ] || continue
         step util pass $i config $c
         timeout -s KILL 120 rocprofv3 --pmc $ok --output-format csv -d "$O/util_c${c}_p$i" -o run -- \
-            python3 "$R/bench.py" $A --no-cpu --no-check --steps 3 --warmup 1 $EXTRA > "$O/util_c${c}_p$i.log" 2>&1 \
+            python3 "$R/bench.py" --full $A --no-cpu --no-check --steps 3 --warmup 1 $EXTRA > "$O/util_c${c}_p$i.log" 2>&1 \
             || { tail -20 "$O/util_c${c}_p$i.log"; exit 1; }
     done
 done

@@ -25,7 +25,7 @@ for C in $CONFIGS; do
     [ -n "$ok" ] || continue
     echo "[$(date +%T)] config $C pass $i:$ok"
     timeout -s KILL 90 rocprofv3 --pmc $ok --output-format csv -d "$O/util_c${C}_p$i" -o run -- \
-        python3 "$R/bench.py" --config "$C" --no-cpu --no-check --steps 3 --warmup 1 > "$O/util_c${C}_p$i.log" 2>&1 \
+        python3 "$R/bench.py" --full --config "$C" --no-cpu --no-check --steps 3 --warmup 1 > "$O/util_c${C}_p$i.log" 2>&1 \
         || { tail -5 "$O/util_c${C}_p$i.log"; exit 1; }
   done
 done
