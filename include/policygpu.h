@@ -278,6 +278,17 @@ int pg_debug_stream_slots(const uint64_t* streams, size_t n, uint32_t* slot_out,
  * code on the host with counting loaders; does not touch the device. */
 int pg_debug_walk_stats(pg_ctx* ctx, int table_id, const pg_tuple_soa* tuples, uint64_t n, uint32_t* lds_reads,
                         uint32_t* mem_reads, int* stage);
+/* TESTS ONLY -- never on the classify path: the launch a SINGLE-mode pg_classify on table_id makes
+ * under the context's launch knobs, with hit counters (counters != 0) or without, from the one
+ * function the launch itself dispatches on (device.hpp single_launch_plan). *stage_code = the
+ * full k_classify STAGE: 4 FD blob in LDS, 5 FD prefix in LDS; 1 blob in LDS, 2 src root in LDS,
+ * 0 nothing staged (linear-flagged tables too); and for tables no rule of which tests dst (the dst
+ * stream is not read) 9, 10, 8 likewise and 14 = a CANDI table's root and window in LDS.
+ * *stage_words = blob words staged; *hist_cells = cells of the LDS hit-counter histogram without
+ * its two extra cells (every slot, or the "hist_window" window; 0 without counters). Any output
+ * may be null. Does not touch the device. */
+int pg_debug_launch_plan(pg_ctx* ctx, int table_id, int counters, int* stage_code, uint32_t* stage_words,
+                         uint32_t* hist_cells);
 /* node classifier (PERPOD / CONN) size: IPv4 classes, L4-key classes, LDS image bytes,
  * cross-table bytes; PG_ENOENT when it was not built */
 int pg_node_stats(pg_ctx* ctx, uint32_t* ip_classes, uint32_t* key_classes, uint64_t* image_bytes,

@@ -207,6 +207,8 @@ _SIGS = {
     "pg_classify_linear": (C.c_int, [_P, C.c_int, C.POINTER(pg_tuple_soa), C.c_uint64, _P, _P]),
     "pg_debug_walk_stats": (C.c_int, [_P, C.c_int, C.POINTER(pg_tuple_soa), C.c_uint64, C.POINTER(C.c_uint32),
                                       C.POINTER(C.c_uint32), C.POINTER(C.c_int)]),
+    "pg_debug_launch_plan": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_uint32),
+                                       C.POINTER(C.c_uint32)]),
     "pg_stream_probe": (C.c_int, [_P, C.c_int, C.POINTER(pg_tuple_soa), C.c_uint64, _P, _P]),
     "pg_counters_device": (_P, [_P]),
     "pg_reset_counters": (C.c_int, [_P, _P]),

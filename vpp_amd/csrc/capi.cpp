@@ -545,6 +545,14 @@ struct CountingLoader {
     W2 u2(uint32_t i) const { return hit(), W2{b[i], b[i + 1]}; }
     W4 u4(uint32_t i) const { return hit(), W4{b[i], b[i + 1], b[i + 2], b[i + 3]}; }
 };
+// the launch a SINGLE pg_classify makes of a compiled table under the context's knobs: the
+// function device.hip launch_classify dispatches on, over the host image of the table set
+LaunchPlan single_plan(const Engine& E, int table_id, bool count) {
+    const HostTableSet& H = E.host;
+    const DevTable& hd = H.tabs[table_id];
+    return single_launch_plan(hd, H.blob_words[table_id], blob_root_words(hd.fsk, hd.nkc), H.blob_prefix[table_id],
+                              (uint32_t)E.slot_table.size(), E.tune, count, dev_candi_lean());
+}
 }  // namespace
 
 extern "C" {
@@ -557,15 +565,11 @@ int pg_debug_walk_stats(pg_ctx* ctx, int table_id, const pg_tuple_soa* t, uint64
     if (!E.compiled) E.compile();
     if (table_id < 0 || (uint32_t)table_id >= E.host.tabs.size()) return fail(ctx, PG_EINVAL, "table id out of range");
     const DevTable& hd = E.host.tabs[table_id];
-    const Tuning& tu = E.tune;
-    const uint32_t words = E.host.blob_words[table_id], prefix = E.host.blob_prefix[table_id];
-    const uint32_t root_words = blob_root_words(hd.fsk, hd.nkc);
     const bool linear = (hd.fsk & kFlagLinear) != 0;
-    // the launch device.hip launch_classify picks for this table (SINGLE mode)
-    int st = 0;
-    if (hd.fsk & kFlagFD) st = words <= tu.stage_max_words ? 4 : (prefix <= tu.stage_root_max_words ? 5 : 0);
-    else if (!linear && words && words <= tu.stage_max_words) st = 1;
-    else if (!linear && words && root_words <= tu.stage_root_max_words) st = 2;
+    // the launch device.hip launch_classify picks for this table (SINGLE mode), as where the
+    // walks below find the blob: without the dst-free mark, and a CANDI root (6) as a root (2)
+    int st = (int)single_plan(E, table_id, false).stage_code;
+    if (st != 4 && st != 5) st = (st & 7) == 6 ? 2 : (st & 7);
     if (stage) *stage = st;
     const uint32_t* blob = E.host.blobs.data() + hd.blob_off;
     for (uint64_t i = 0; i < n; i++) {
@@ -602,6 +606,21 @@ int pg_debug_walk_stats(pg_ctx* ctx, int table_id, const pg_tuple_soa* t, uint64
         lds_reads[i] = nl;
         mem_reads[i] = nm;
     }
+    return PG_OK;
+    GUARD_END(ctx)
+}
+
+int pg_debug_launch_plan(pg_ctx* ctx, int table_id, int counters, int* stage_code, uint32_t* stage_words,
+                         uint32_t* hist_cells) {
+    if (!ctx) return PG_EINVAL;
+    GUARD_BEGIN
+    Engine& E = ctx->eng;
+    if (!E.compiled) E.compile();
+    if (table_id < 0 || (uint32_t)table_id >= E.host.tabs.size()) return fail(ctx, PG_EINVAL, "table id out of range");
+    const LaunchPlan p = single_plan(E, table_id, counters != 0);
+    if (stage_code) *stage_code = (int)p.stage_code;
+    if (stage_words) *stage_words = p.stage_words;
+    if (hist_cells) *hist_cells = p.hist_cells;
     return PG_OK;
     GUARD_END(ctx)
 }

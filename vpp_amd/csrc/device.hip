@@ -432,6 +432,7 @@ constexpr size_t kLdsPerCU = 160u << 10;
 #ifndef PG_CANDI_LEAN  // SINGLE over a CANDI table with its root staged: the dedicated walk (STAGE 6)
 #define PG_CANDI_LEAN 1
 #endif
+bool dev_candi_lean() { return PG_CANDI_LEAN != 0; }
 #ifndef PG_QSINGLE_LDS
 #define PG_QSINGLE_LDS 1
 #endif
@@ -1290,35 +1291,40 @@ static void launch_one(const DevTableSet& T, const Tuning& tu, int t, const uint
                                                   cells, stage, items);
 }
 
-// SINGLE over a non-FD table: the blob in LDS (STAGE 1), its root in LDS (2) or all in HBM (0);
+// SINGLE over a non-FD table, at the stage single_launch_plan (device.hpp) chose: the blob in LDS
+// (STAGE 1), a CANDI table's root and window in LDS (6), its root in LDS (2) or all in HBM (0);
 // NODST = 8 for dst-free tables
 template <int MODE, bool COUNT, bool VEC, int NODST>
 static void launch_generic(const DevTableSet& T, const Tuning& tu, int t, const uint32_t* src, const uint32_t* dst,
                            const uint16_t* sport, const uint16_t* dport, const uint8_t* proto, uint64_t n,
-                           uint32_t* out, unsigned long long* counters, hipStream_t st, size_t hist, uint32_t cells,
-                           uint32_t words, uint32_t root_words, uint64_t items) {
-    const DevTable& hd = T.host_tabs[t];
-    if (!(hd.fsk & kFlagLinear) && words && words <= tu.stage_max_words)
-        launch_one<MODE, COUNT, VEC, 1 + NODST, false>(T, tu, t, src, dst, sport, dport, proto, n, out, counters, st,
-                                                       hist, cells, words, items);
-    else if ((hd.fsk & kFlagCandI) && NODST && PG_CANDI_LEAN && root_words <= tu.stage_root_max_words)
-        launch_one<MODE, COUNT, VEC, 6 + NODST, false>(T, tu, t, src, dst, sport, dport, proto, n, out, counters, st,
-                                                       hist, cells, root_words, items);
-    else if (!(hd.fsk & kFlagLinear) && words && root_words <= tu.stage_root_max_words)
-        launch_one<MODE, COUNT, VEC, 2 + NODST, false>(T, tu, t, src, dst, sport, dport, proto, n, out, counters, st,
-                                                       hist, cells, root_words, items);
-    else
-        launch_one<MODE, COUNT, VEC, 0 + NODST, false>(T, tu, t, src, dst, sport, dport, proto, n, out, counters, st,
-                                                       hist, cells, 0, items);
+                           uint32_t* out, unsigned long long* counters, hipStream_t st, const LaunchPlan& p,
+                           uint64_t items) {
+    const size_t hist = p.hist_bytes;
+    const uint32_t cells = p.hist_cells, words = p.stage_words;
+    switch ((int)p.stage_code - NODST) {
+    case 1:
+        return launch_one<MODE, COUNT, VEC, 1 + NODST, false>(T, tu, t, src, dst, sport, dport, proto, n, out, counters,
+                                                              st, hist, cells, words, items);
+    case 6:
+        return launch_one<MODE, COUNT, VEC, 6 + NODST, false>(T, tu, t, src, dst, sport, dport, proto, n, out, counters,
+                                                              st, hist, cells, words, items);
+    case 2:
+        return launch_one<MODE, COUNT, VEC, 2 + NODST, false>(T, tu, t, src, dst, sport, dport, proto, n, out, counters,
+                                                              st, hist, cells, words, items);
+    default:
+        return launch_one<MODE, COUNT, VEC, 0 + NODST, false>(T, tu, t, src, dst, sport, dport, proto, n, out, counters,
+                                                              st, hist, cells, 0, items);
+    }
 }
 
 template <int MODE, bool COUNT, bool VEC>
 static void launch_classify(const DevTableSet& T, const Tuning& tu, int t, const uint32_t* src, const uint32_t* dst,
                             const uint16_t* sport, const uint16_t* dport, const uint8_t* proto, uint64_t n,
                             uint32_t* out, unsigned long long* counters, hipStream_t st) {
-    // hit-counter LDS histogram (k_classify): every slot + 2 cells; or (more slots than fit) a
-    // SINGLE table's window of hist_window cells + 2; or a node set's slot cache (node_hist_cells
-    // rounded down to a power of two; 0 = global atomics only)
+    // hit-counter LDS histogram (k_classify) of PERPOD / CONN launches (SINGLE: single_launch_plan
+    // below): every slot + 2 cells; or (more slots than fit) without the node classifier a window of
+    // hist_window cells + 2, with it the node set's slot cache (node_hist_cells rounded down to a
+    // power of two; 0 = global atomics only)
     const bool node = MODE != 0 && tu.node_path && T.node.img;
     uint32_t cells = 0;
     size_t hist = 0;
@@ -1327,7 +1333,7 @@ static void launch_classify(const DevTableSet& T, const Tuning& tu, int t, const
     // the LDS budget of two workgroups per CU (node_common_lds_max)
     const bool half = PG_NODE_HALF && COUNT && node && PG_NODE_FULLH && T.node.uniform && T.n_slots <= kLdsHistMax - 2u &&
                       ((size_t)T.n_slots + 2u) * 4 + (size_t)T.node.img_words_base * 4 > tu.node_common_lds_max;
-    if (COUNT) {
+    if (COUNT && MODE != 0) {
         if (half) {
             cells = T.n_slots;
             hist = ((size_t)(cells + 1u) / 2u + 1u) * 4;
@@ -1344,22 +1350,21 @@ static void launch_classify(const DevTableSet& T, const Tuning& tu, int t, const
     }
     const uint64_t items = VEC ? (n + tuples_per_lane<MODE>() - 1) / tuples_per_lane<MODE>() : n;
     if constexpr (MODE == 0) {
+        // the stage and the histogram (every slot + 2 cells, or a window of hist_window cells + 2)
+        // by the one host-only plan function tests can query (device.hpp single_launch_plan)
         const DevTable& hd = T.host_tabs[t];
-        const uint32_t words = T.host_blob_words[t];
-        const uint32_t root_words = blob_root_words(hd.fsk, hd.nkc);  // (CANDI: + its window)
-        const uint32_t prefix = T.host_blob_prefix[t];
-        if ((hd.fsk & kFlagFD) && words <= tu.stage_max_words)  // FD blob in LDS, no dst stream
-            launch_one<MODE, COUNT, VEC, 4, false>(T, tu, t, src, dst, sport, dport, proto, n, out, counters, st, hist,
-                                                   cells, words, items);
-        else if ((hd.fsk & kFlagFD) && prefix <= tu.stage_root_max_words)  // its prefix in LDS, the rest in HBM
-            launch_one<MODE, COUNT, VEC, 5, false>(T, tu, t, src, dst, sport, dport, proto, n, out, counters, st, hist,
-                                                   cells, prefix, items);
-        else if (hd.fsk & kFlagDstFree)  // no rule tests dst: the dst stream is not read
-            launch_generic<MODE, COUNT, VEC, 8>(T, tu, t, src, dst, sport, dport, proto, n, out, counters, st, hist,
-                                                cells, words, root_words, items);
+        const LaunchPlan p = single_launch_plan(hd, T.host_blob_words[t], blob_root_words(hd.fsk, hd.nkc) /* (CANDI: + its window) */,
+                                                T.host_blob_prefix[t], T.n_slots, tu, COUNT, dev_candi_lean());
+        if (p.stage_code == 4)  // FD blob in LDS, no dst stream
+            launch_one<MODE, COUNT, VEC, 4, false>(T, tu, t, src, dst, sport, dport, proto, n, out, counters, st,
+                                                   p.hist_bytes, p.hist_cells, p.stage_words, items);
+        else if (p.stage_code == 5)  // its prefix in LDS, the rest in HBM
+            launch_one<MODE, COUNT, VEC, 5, false>(T, tu, t, src, dst, sport, dport, proto, n, out, counters, st,
+                                                   p.hist_bytes, p.hist_cells, p.stage_words, items);
+        else if (p.stage_code & 8)  // no rule tests dst: the dst stream is not read
+            launch_generic<MODE, COUNT, VEC, 8>(T, tu, t, src, dst, sport, dport, proto, n, out, counters, st, p, items);
         else
-            launch_generic<MODE, COUNT, VEC, 0>(T, tu, t, src, dst, sport, dport, proto, n, out, counters, st, hist,
-                                                cells, words, root_words, items);
+            launch_generic<MODE, COUNT, VEC, 0>(T, tu, t, src, dst, sport, dport, proto, n, out, counters, st, p, items);
     } else if (node) {
         // the image with its common-row section and dst records when that fits the LDS budget
         // next to the histogram, else without the records (the kernel then reads them from the

@@ -14,6 +14,8 @@
 #include <string>
 #include <vector>
 
+#include "blobwalk.hpp"  // table flags (kFlag*)
+
 namespace pg {
 
 // Packet L4 key: TCP -> dport, UDP -> 0x10000|dport, OTHER -> 0x20000, else (ANY/invalid) 0x30000.
@@ -255,6 +257,40 @@ struct Tuning {
     uint32_t hist_window = 4096;   // LDS hit-counter cells when the slots exceed the LDS histogram
     uint32_t launch_max_tuples = 0;  // tuples per k_classify launch at most (0 = kMaxLaunchTuples)
 };
+// The launch a SINGLE classify makes of one table: the k_classify STAGE its blob is walked
+// at and the hit-counter LDS histogram (device.hip launch_classify dispatches on it;
+// pg_debug_walk_stats / pg_debug_launch_plan report it to tests). Host only, no HIP types.
+//   stage_code  4 = an FD blob whole in LDS, 5 = its prefix in LDS; else the generic walk: 1 = the
+//               blob in LDS, 6 = a CANDI table's root (+ window) in LDS, 2 = the src root in
+//               LDS, 0 = all in HBM (linear-flagged tables too) -- + 8 when no rule tests dst
+//               (the dst stream is not read; 6 only as 14)
+//   stage_words blob words copied into LDS
+//   hist_cells  with counters: every slot of the set, or (more than kLdsHistCells slots) a window
+//               of hist_window cells; hist_bytes: its LDS bytes with the two extra cells
+struct LaunchPlan {
+    uint32_t stage_code, stage_words, hist_cells, hist_bytes;
+};
+// words / prefix: HostTableSet blob_words / blob_prefix of the table; root_words:
+// blob_root_words (blobwalk.hpp); candi_lean: the library's PG_CANDI_LEAN (dev_candi_lean below)
+inline LaunchPlan single_launch_plan(const DevTable& hd, uint32_t words, uint32_t root_words, uint32_t prefix,
+                                     uint32_t n_slots, const Tuning& tu, bool count, bool candi_lean) {
+    LaunchPlan p{};
+    if (count) {
+        p.hist_cells = n_slots <= kLdsHistCells ? n_slots : (tu.hist_window < kLdsHistCells ? tu.hist_window : kLdsHistCells);
+        p.hist_bytes = (p.hist_cells + 2u) * 4u;
+    }
+    const uint32_t nodst = (hd.fsk & kFlagDstFree) ? 8u : 0u;
+    const bool walk = !(hd.fsk & kFlagLinear) && words;
+    if ((hd.fsk & kFlagFD) && words <= tu.stage_max_words) p.stage_code = 4, p.stage_words = words;
+    else if ((hd.fsk & kFlagFD) && prefix <= tu.stage_root_max_words) p.stage_code = 5, p.stage_words = prefix;
+    else if (walk && words <= tu.stage_max_words) p.stage_code = 1 + nodst, p.stage_words = words;
+    else if ((hd.fsk & kFlagCandI) && nodst && candi_lean && root_words <= tu.stage_root_max_words)
+        p.stage_code = 6 + nodst, p.stage_words = root_words;
+    else if (walk && root_words <= tu.stage_root_max_words) p.stage_code = 2 + nodst, p.stage_words = root_words;
+    else p.stage_code = nodst;
+    return p;
+}
+
 // key -> field; 0 ok, -1 unknown key or value out of range. *compiler: the key changes how
 // tables are compiled (the context recompiles on its next use).
 int tuning_set(Tuning& t, const std::string& key, int value, bool* compiler = nullptr);
@@ -312,6 +348,9 @@ DeviceBuffers* dev_upload(const HostTableSet& h, std::string* err);
 void dev_free(DeviceBuffers* b);
 const DevTableSet& dev_view(const DeviceBuffers* b);
 
+// the build's PG_CANDI_LEAN (device.hip: SINGLE over a CANDI table with its root staged takes the
+// dedicated walk, STAGE 6) -- what single_launch_plan is given, by the launch and by tests alike
+bool dev_candi_lean();
 int dev_classify(const DevTableSet& T, const Tuning& tu, int mode, int table_id, const uint32_t* src,
                  const uint32_t* dst, const uint16_t* sport, const uint16_t* dport, const uint8_t* proto, uint64_t n,
                  uint32_t* out, unsigned long long* counters, void* stream, std::string* err);

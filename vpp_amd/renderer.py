@@ -318,6 +318,14 @@ class Engine:
                                          nm.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(st)))
         return nl, nm, st.value
 
+    def debug_launch_plan(self, table_id, counters=False):
+        """TESTS ONLY: the launch a SINGLE classify on table_id makes under this context's knobs
+        (pg_debug_launch_plan) -> {stage: the full k_classify STAGE code (4, 5, 1, 2, 0; dst-free
+        tables 9, 10, 14, 8), stage_words, hist_cells}"""
+        st, sw, hc = C.c_int(), C.c_uint32(), C.c_uint32()
+        self._ck(lib.pg_debug_launch_plan(self.h, table_id, int(counters), C.byref(st), C.byref(sw), C.byref(hc)))
+        return {"stage": st.value, "stage_words": sw.value, "hist_cells": hc.value}
+
     def node_stats(self):
         """node classifier size {ip_classes, key_classes, image_bytes, cross_bytes}, or None."""
         a, b = C.c_uint32(), C.c_uint32()
