@@ -289,6 +289,35 @@ int pg_debug_walk_stats(pg_ctx* ctx, int table_id, const pg_tuple_soa* tuples, u
  * may be null. Does not touch the device. */
 int pg_debug_launch_plan(pg_ctx* ctx, int table_id, int counters, int* stage_code, uint32_t* stage_words,
                          uint32_t* hist_cells);
+/* TESTS ONLY -- never on the classify path: the launch a PERPOD / CONN pg_classify makes of the
+ * compiled table set under the context's launch knobs, with hit counters (counters != 0) or
+ * without, from the one function the launch itself dispatches on (device.hpp node_launch_plan).
+ *   path            1 = the node classifier, 0 = the per-table path ("node_path" 0, or no node)
+ *   stage_code      the full k_classify STAGE of the node kernel: 3 = the node image with its
+ *                   common-row section staged in LDS, 1 = the base image staged, 0 = the image
+ *                   read from HBM; + 32 node sets without PAIR tables, + 96 the uniform layout,
+ *                   + 96 + 128 with wide records; + 16 counters in an LDS histogram of every
+ *                   slot, + 16 + 256 in 16-bit cells. Per-table path: 0
+ *   stage_words     image words staged
+ *   records_staged  1 = the dst records are read from the image (staged with it, or with
+ *                   stage_code 0 from HBM), 0 = from the cross array (or there are none)
+ *   hist_kind       PG_HIST_*: no counters; every slot in 32-bit LDS cells; every slot in 16-bit
+ *                   LDS cells; the node's LDS slot cache ("node_hist_cells", sets of more than
+ *                   16382 slots); global atomics only; the first "hist_window" slots in LDS (the
+ *                   per-table path over such a set)
+ *   hist_cells      LDS cells without the scheme's extra cells; hist_bytes: its LDS bytes
+ *   defers_any      1 = a k_node_any launch follows for the ANY-protocol packets
+ * mode: PG_MODE_PERPOD or PG_MODE_CONN. Does not touch the device. */
+enum { PG_HIST_NONE = 0, PG_HIST_FULL32 = 1, PG_HIST_HALF16 = 2, PG_HIST_CACHE = 3, PG_HIST_GLOBAL = 4,
+       PG_HIST_WINDOW = 5 };
+typedef struct pg_node_launch_plan {
+    int path, stage_code;
+    uint32_t stage_words;
+    int records_staged, hist_kind;
+    uint32_t hist_cells, hist_bytes;
+    int defers_any;
+} pg_node_launch_plan;
+int pg_debug_node_launch_plan(pg_ctx* ctx, int mode, int counters, pg_node_launch_plan* plan);
 /* node classifier (PERPOD / CONN) size: IPv4 classes, L4-key classes, LDS image bytes,
  * cross-table bytes; PG_ENOENT when it was not built */
 int pg_node_stats(pg_ctx* ctx, uint32_t* ip_classes, uint32_t* key_classes, uint64_t* image_bytes,

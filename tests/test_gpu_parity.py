@@ -527,8 +527,12 @@ def test_k8s_object_cluster_gpu_vs_oracle(mode):
     assert len(np.unique(got >> 30)) >= 2
 
 
-def _classify_with(e, mode, b, node_path, stage_words=16384, counters=False, common_lds=80 << 10):
+def _classify_with(e, mode, b, node_path, stage_words=16384, counters=False, common_lds=80 << 10, plan=None):
+    """plan: (STAGE & 7, records_staged, hist_kind) the launch must take (pg_debug_node_launch_plan)"""
     with e.tuning(node_path=node_path, node_stage_max_words=stage_words, node_common_lds_max=common_lds):
+        if plan is not None:
+            p = e.debug_node_launch_plan(mode, counters)
+            assert (p["stage"] & 7, p["records_staged"], p["hist_kind"]) == plan and p["path"] == "node", (p, plan)
         out = torch.empty(b.n, dtype=torch.int32, device="cuda")
         cnt = torch.zeros(e.num_counter_slots(), dtype=torch.int64, device="cuda") if counters else None
         D.classify(e, mode, -1, b, out, counters=cnt)
@@ -547,15 +551,17 @@ def test_node_kernel_equals_per_table_kernel(config):
     assert e.node_stats() is not None
     b = D.TupleBatch(w.n_tuples, with_sport=True)
     D.gen_tuples(e, b, **w.gen)
-    staged, c1 = _classify_with(e, w.mode, b, 1, counters=True)
-    hbm, c2 = _classify_with(e, w.mode, b, 1, stage_words=0, counters=True)
+    staged, c1 = _classify_with(e, w.mode, b, 1, counters=True, plan=(3, False, "full32"))
+    # (the image is larger than the 8192 words a launch stages at STAGE 3 past node_stage_max_words)
+    hbm, c2 = _classify_with(e, w.mode, b, 1, stage_words=0, counters=True, plan=(0, False, "full32"))
     table, c3 = _classify_with(e, w.mode, b, 0, counters=True)
     assert np.array_equal(staged, hbm) and np.array_equal(staged, table)
     assert np.array_equal(c1, c2) and np.array_equal(c1, c3)
-    # the image's common-row section staged next to the histogram (STAGE 3), and left out
-    common, c4 = _classify_with(e, w.mode, b, 1, counters=True, common_lds=160 << 10)
-    base, c5 = _classify_with(e, w.mode, b, 1, counters=True, common_lds=0)
-    nocnt, _ = _classify_with(e, w.mode, b, 1)  # STAGE 3 at the default budget
+    # the image's common-row section staged next to the histogram (STAGE 3), and left out: the base
+    # image (STAGE 1) -- with a budget of 0 beside the 16-bit-cell histogram (every uniform set's then)
+    common, c4 = _classify_with(e, w.mode, b, 1, counters=True, common_lds=160 << 10, plan=(3, False, "full32"))
+    base, c5 = _classify_with(e, w.mode, b, 1, counters=True, common_lds=0, plan=(1, False, "half16"))
+    nocnt, _ = _classify_with(e, w.mode, b, 1, plan=(3, False, "none"))  # STAGE 3 at the default budget
     assert np.array_equal(common, staged) and np.array_equal(base, staged) and np.array_equal(nocnt, staged)
     assert np.array_equal(c4, c1) and np.array_equal(c5, c1)
     host = e.debug_classify_host(w.mode, -1, *b.numpy(b.n), node=True)
@@ -584,7 +590,8 @@ def test_node_launch_variants(config):
     with e.tuning(node_common=0):  # the table form without common rows (STAGE 1)
         assert e.node_stats()["common_row_pairs"] == 0
         for counters in (True, False):
-            got, c = _classify_with(e, w.mode, b, 1, counters=counters)
+            got, c = _classify_with(e, w.mode, b, 1, counters=counters,
+                                    plan=(1, False, "full32" if counters else "none"))
             assert np.array_equal(got, ref) and (not counters or np.array_equal(c, cref))
     with e.tuning(node_list_table=0):
         ns = e.node_stats()
@@ -592,20 +599,27 @@ def test_node_launch_variants(config):
         norec = ns["image_bytes"] - ns["list_record_bytes"]
         for counters in (True, False):
             h = hist if counters else 0
-            got, c = _classify_with(e, w.mode, b, 1, counters=counters)  # everything staged
+            kind = "full32" if counters else "none"
+            # the default budget: everything staged without counters; beside the histogram the
+            # records no longer fit (lrec cleared)
+            got, c = _classify_with(e, w.mode, b, 1, counters=counters, plan=(3, not counters, kind))
             assert np.array_equal(got, ref) and (not counters or np.array_equal(c, cref))
+            got, c = _classify_with(e, w.mode, b, 1, counters=counters, common_lds=160 << 10, plan=(3, True, kind))
+            assert np.array_equal(got, ref) and (not counters or np.array_equal(c, cref))  # everything staged
             # the common rows staged, the records not (lrec cleared: read from the cross array)
-            got, c = _classify_with(e, w.mode, b, 1, counters=counters, common_lds=h + norec + 16)
+            got, c = _classify_with(e, w.mode, b, 1, counters=counters, common_lds=h + norec + 16,
+                                    plan=(3, False, kind))
             assert np.array_equal(got, ref) and (not counters or np.array_equal(c, cref))
         with e.tuning(node_common=0):
             ns2 = e.node_stats()
             assert ns2["common_row_pairs"] == 0 and ns2["list_records_in_image"]
             base = ns2["base_image_bytes"] // 4
             for counters in (True, False):
-                got, c = _classify_with(e, w.mode, b, 1, counters=counters)  # STAGE 1, records staged
+                kind = "full32" if counters else "none"
+                got, c = _classify_with(e, w.mode, b, 1, counters=counters, plan=(1, True, kind))  # STAGE 1, records staged
                 assert np.array_equal(got, ref) and (not counters or np.array_equal(c, cref))
                 # STAGE 1 with the base image only: records from the cross array
-                got, c = _classify_with(e, w.mode, b, 1, stage_words=base, counters=counters)
+                got, c = _classify_with(e, w.mode, b, 1, stage_words=base, counters=counters, plan=(1, False, kind))
                 assert np.array_equal(got, ref) and (not counters or np.array_equal(c, cref))
 
 

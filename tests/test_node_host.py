@@ -20,9 +20,11 @@ from vpp_amd import workloads as W
 from vpp_amd._capi import MODE_CONN, MODE_PERPOD
 
 
-def topology(rnd, n_pods=14, weird=False, big=False):
+def topology(rnd, n_pods=14, weird=False, big=False, open_tail=False):
     """Local pods with random inbound/outbound ACLs on their TAPs (some reflective), two
-    remote pods, one pod without an interface, and ACLs on the node-output interface."""
+    remote pods, one pod without an interface, and ACLs on the node-output interface.
+    open_tail: every third pod's outbound ACL ends without its deny-the-rest rule, so packets
+    reach the table's default-deny slot."""
     e = R.Engine(0)
     e.SetMainInterfaceName("GbE")
     e.SetVxlanBVIIfName("VXLAN-BVI")
@@ -48,12 +50,15 @@ def topology(rnd, n_pods=14, weird=False, big=False):
                                                             "egress": []}))
         if rnd.random() < 0.8:
             outb = fz.rand_acl(rnd, rnd.randint(0, 40), fz.ANCHORS + pod_ips, weird, tail="deny")
+            if open_tail and k % 3 == 0:
+                outb.pop()
             ops.append(("config/vpp/acls/v2/acl/out-" + ifn, {"name": "out-" + ifn, "rules": outb, "ingress": [],
                                                              "egress": [ifn]}))
     glob = fz.rand_acl(rnd, 30, fz.ANCHORS + pod_ips, weird, tail="permit")
     if big:  # one table past the cross-product limit (candidate mode): not covered by the node
+        # (big = a number: that many rules, for a lower cross_max_rules -- tests/node_matrix.py)
         glob = [{"action": k % 2, "src": "10.%d.%d.0/24" % (k // 256, k % 256), "dst": "",
-                 "udp": {"src": [0, 65535], "dst": [k % 1000, k % 1000 + 5]}} for k in range(17000)] + glob
+                 "udp": {"src": [0, 65535], "dst": [k % 1000, k % 1000 + 5]}} for k in range(17000 if big is True else big)] + glob
     ops.append(("config/vpp/acls/v2/acl/g", {"name": "g", "rules": glob, "ingress": [], "egress": ["VXLAN-BVI"]}))
     e.ApplyTxn(True, ops)
     return e, (local, no_if), pod_ips
@@ -235,9 +240,13 @@ def test_config9_more_than_254_tables_wide_records():
     assert len(set((got >> 30).tolist())) >= 3
 
 
-def _many_tables(n_tables, seed):
+def _many_tables(n_tables, seed, extra_pods=False, rules=0):
     """n_tables - 1 local pods, each with its own small outbound ACL, and a global ACL on the
-    node-output interface: n_tables tables, every one covered by the node."""
+    node-output interface: n_tables tables, every one covered by the node. extra_pods: also a
+    local pod without ACLs, a pod without an interface and a remote pod (no table more), and
+    every third outbound ACL without its final deny rule. rules: that many rules per outbound
+    ACL instead of 1 to 3, each a different (one of the first 32 pods, TCP / UDP, popular port):
+    more counter slots over the same few node classes."""
     rnd = random.Random(seed)
     e = R.Engine(0)
     e.SetMainInterfaceName("GbE")
@@ -252,20 +261,35 @@ def _many_tables(n_tables, seed):
         e.RegisterPod("ns/p%d" % k, W.ip_str(ip), False)
         local[ip] = ifn
         outb = []  # from a few pods, a few popular ports: a cross product the node keeps small
-        for _ in range(rnd.randint(1, 3)):
+        grid = [(j, l4, p) for j in range(32) for l4 in ("tcp", "udp") for p in (80, 443, 8080)]
+        for j, l4, p in rnd.sample(grid, rules):
+            outb.append({"action": rnd.choice([0, 1, 1, 2]), "src": W.ip_str(0x0A0B0000 | (j + 1)) + "/32", "dst": "",
+                         l4: {"src": [0, 65535], "dst": [p, p]}})
+        for _ in range(0 if rules else rnd.randint(1, 3)):
             r = {"action": rnd.choice([0, 1, 1, 2]), "src": W.ip_str(rnd.choice(pod_ips)) + "/32", "dst": ""}
             if rnd.random() < 0.7:
                 p = rnd.choice([80, 443, 8080])
                 r[rnd.choice(["tcp", "udp"])] = {"src": [0, 65535], "dst": [p, p]}
             outb.append(r)
-        outb.append({"action": 0, "src": "", "dst": ""})
+        if not (extra_pods and k % 3 == 0):  # (extra_pods: every third table's default-deny slot is reachable)
+            outb.append({"action": 0, "src": "", "dst": ""})
         ops.append(("config/vpp/acls/v2/acl/out-" + ifn, {"name": "out-" + ifn, "rules": outb, "ingress": [],
                                                          "egress": [ifn]}))
     glob = [{"action": k % 2, "src": W.ip_str(pod_ips[k]) + "/32", "dst": ""} for k in range(12)]
     glob.append({"action": 1, "src": "", "dst": ""})
     ops.append(("config/vpp/acls/v2/acl/g", {"name": "g", "rules": glob, "ingress": [], "egress": ["VXLAN-BVI"]}))
+    no_if = []
+    if extra_pods:
+        bare, lost, far = 0x0A0C0001, 0x0A0C0002, 0x0A0C0003
+        e.SetPodIfName("ns/bare", "tap-bare")
+        e.RegisterPod("ns/bare", W.ip_str(bare), False)
+        local[bare] = "tap-bare"
+        e.RegisterPod("ns/lost", W.ip_str(lost), False)
+        e.RegisterPod("ns/far", W.ip_str(far), True)
+        no_if.append(lost)
+        pod_ips += [bare, lost, far]
     e.ApplyTxn(True, ops)
-    return e, (local, []), pod_ips
+    return e, (local, no_if), pod_ips
 
 
 @pytest.mark.parametrize("n_tables", [251, 252, 253, 255, 256])

@@ -70,6 +70,12 @@ class pg_gen_spec(C.Structure):
                 ("zipf_cdf", C.POINTER(C.c_uint32)), ("nomatch_pct", C.c_uint32), ("dst_pool_pct", C.c_uint32)]
 
 
+class pg_node_launch_plan(C.Structure):
+    _fields_ = [("path", C.c_int), ("stage_code", C.c_int), ("stage_words", C.c_uint32), ("records_staged", C.c_int),
+                ("hist_kind", C.c_int), ("hist_cells", C.c_uint32), ("hist_bytes", C.c_uint32),
+                ("defers_any", C.c_int)]
+
+
 class pg_conn_query(C.Structure):
     _fields_ = [("kind", C.c_int32), ("src_namespace", C.c_char_p), ("src_name", C.c_char_p),
                 ("dst_namespace", C.c_char_p), ("dst_name", C.c_char_p), ("src_ip", C.c_char_p),
@@ -209,6 +215,7 @@ _SIGS = {
                                       C.POINTER(C.c_uint32), C.POINTER(C.c_int)]),
     "pg_debug_launch_plan": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_uint32),
                                        C.POINTER(C.c_uint32)]),
+    "pg_debug_node_launch_plan": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(pg_node_launch_plan)]),
     "pg_stream_probe": (C.c_int, [_P, C.c_int, C.POINTER(pg_tuple_soa), C.c_uint64, _P, _P]),
     "pg_counters_device": (_P, [_P]),
     "pg_reset_counters": (C.c_int, [_P, _P]),

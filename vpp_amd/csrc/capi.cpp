@@ -624,6 +624,27 @@ int pg_debug_launch_plan(pg_ctx* ctx, int table_id, int counters, int* stage_cod
     return PG_OK;
     GUARD_END(ctx)
 }
+
+int pg_debug_node_launch_plan(pg_ctx* ctx, int mode, int counters, pg_node_launch_plan* plan) {
+    if (!ctx || !plan || (mode != PG_MODE_PERPOD && mode != PG_MODE_CONN)) return PG_EINVAL;
+    GUARD_BEGIN
+    Engine& E = ctx->eng;
+    if (!E.compiled) E.compile();
+    // the function device.hip launch_classify<1|2> dispatches on, over the host image of the set
+    DevNode nd = E.host.node;
+    nd.img = E.host.node_img.empty() ? nullptr : E.host.node_img.data();
+    const NodeLaunchPlan p = node_launch_plan(nd, (uint32_t)E.slot_table.size(), mode, counters != 0, E.tune, dev_node_build());
+    plan->path = (int)p.path;
+    plan->stage_code = (int)p.stage_code;
+    plan->stage_words = p.stage_words;
+    plan->records_staged = (int)p.records_staged;
+    plan->hist_kind = (int)p.hist_kind;
+    plan->hist_cells = p.hist_cells;
+    plan->hist_bytes = p.hist_bytes;
+    plan->defers_any = (int)p.defers_any;
+    return PG_OK;
+    GUARD_END(ctx)
+}
 }  // extern "C"
 
 namespace {

@@ -371,7 +371,6 @@ int dev_comm_allreduce_u64(void* const* comms, unsigned long long* const* bufs, 
 }
 
 constexpr int kBlock = 256;
-constexpr uint32_t kLdsHistMax = kLdsHistCells + 2;  // hit-counter cells kept in LDS (64 KiB): a window + 2
 
 // Tuple streams are read once and verdicts written once: issued with the non-temporal
 // policy (A/B in one process with tools/sweep.py: +3-4 % on config 2; PG_NT_STREAM=0 builds
@@ -503,6 +502,9 @@ bool dev_candi_lean() { return PG_CANDI_LEAN != 0; }
 #endif
 template <int MODE>
 constexpr bool defer_any() { return MODE == 2 ? PG_CONN_DEFER_ANY : (MODE == 1 ? PG_POD_DEFER_ANY : false); }
+NodeBuild dev_node_build() {
+    return NodeBuild{PG_NODE_FULLH != 0, PG_NODE_HALF != 0, PG_NODE_NOPAIR != 0, PG_CONN_DEFER_ANY != 0, PG_POD_DEFER_ANY != 0};
+}
 // any of the four protocol bytes of w above 2 (bytes >= 0x80 by their top bit, the rest by a
 // carry-free add into it)
 __device__ __forceinline__ bool any_proto_gt2(uint32_t w) {
@@ -788,7 +790,7 @@ void k_classify(DevTableSet T, int32_t t, const uint32_t* __restrict__ src,
     // hit counters: an LDS histogram of the window [wbase, wbase + wn) of slots plus cells for
     // slots xslot and xslot1, flushed with one u64 atomic per non-zero cell; slots outside go to
     // global atomics. Every slot fits the window unless the table set has more than
-    // kLdsHistMax - 2; then the window is a SINGLE table's first rules (first-match traffic
+    // kLdsHistCells; then the window is a SINGLE table's first rules (first-match traffic
     // favours them: config 4's Zipf depth) and the extra cells its default-deny slot and its
     // last rule (a deny-the-rest / allow-all catch-all takes every unmatched packet: a single
     // global address would serialise them); node modes: "no ACL", "unresolved"
@@ -1179,7 +1181,7 @@ __global__ void k_conn_queries(DevTableSet T, const ConnQueryDev* q, uint32_t n,
 // entries), node_path, node_common_lds_max (LDS bytes -- image + counter histogram -- up to
 // which a node image's common-row section is staged: 80 KiB keeps two 512-thread workgroups
 // per CU), block_stage (workgroup size of LDS-staged launches; 0 = per mode).
-constexpr uint32_t kCommonStageExtraWords = 8192;  // the section may take the image past the base cap
+// (kCommonStageExtraWords, device.hpp: the common-row section may take the image past the base cap)
 
 // CUs of the current device (per device: contexts on different GPUs share the process)
 static uint32_t num_cus() {
@@ -1321,33 +1323,13 @@ template <int MODE, bool COUNT, bool VEC>
 static void launch_classify(const DevTableSet& T, const Tuning& tu, int t, const uint32_t* src, const uint32_t* dst,
                             const uint16_t* sport, const uint16_t* dport, const uint8_t* proto, uint64_t n,
                             uint32_t* out, unsigned long long* counters, hipStream_t st) {
-    // hit-counter LDS histogram (k_classify) of PERPOD / CONN launches (SINGLE: single_launch_plan
-    // below): every slot + 2 cells; or (more slots than fit) without the node classifier a window of
-    // hist_window cells + 2, with it the node set's slot cache (node_hist_cells rounded down to a
-    // power of two; 0 = global atomics only)
-    const bool node = MODE != 0 && tu.node_path && T.node.img;
-    uint32_t cells = 0;
-    size_t hist = 0;
-    // node sets counted into 16-bit cells (k_classify STAGE + 256): the uniform layout, every
-    // slot in the histogram, and a 32-bit histogram that even beside the base image would exceed
-    // the LDS budget of two workgroups per CU (node_common_lds_max)
-    const bool half = PG_NODE_HALF && COUNT && node && PG_NODE_FULLH && T.node.uniform && T.n_slots <= kLdsHistMax - 2u &&
-                      ((size_t)T.n_slots + 2u) * 4 + (size_t)T.node.img_words_base * 4 > tu.node_common_lds_max;
-    if (COUNT && MODE != 0) {
-        if (half) {
-            cells = T.n_slots;
-            hist = ((size_t)(cells + 1u) / 2u + 1u) * 4;
-        } else if (T.n_slots <= kLdsHistMax - 2u) {
-            cells = T.n_slots;
-            hist = ((size_t)cells + 2u) * 4;
-        } else if (!node) {
-            cells = std::min(tu.hist_window, kLdsHistMax - 2u);
-            hist = ((size_t)cells + 2u) * 4;
-        } else if (tu.node_hist_cells >= 16u) {  // the slot cache: 2^k cells of {key, count} + the hot cell
-            cells = 1u << (31 - __builtin_clz(tu.node_hist_cells));
-            hist = ((size_t)cells + 1u) * 8;
-        }
-    }
+    // PERPOD / CONN: the path, the node kernel family and staging, and the hit-counter scheme by
+    // the one host-only plan function tests can query (device.hpp node_launch_plan; SINGLE:
+    // single_launch_plan below)
+    const NodeLaunchPlan np = node_launch_plan(T.node, T.n_slots, MODE, COUNT, tu, dev_node_build());
+    const bool node = np.path != 0;
+    const uint32_t cells = np.hist_cells;
+    const size_t hist = np.hist_bytes;
     const uint64_t items = VEC ? (n + tuples_per_lane<MODE>() - 1) / tuples_per_lane<MODE>() : n;
     if constexpr (MODE == 0) {
         // the stage and the histogram (every slot + 2 cells, or a window of hist_window cells + 2)
@@ -1370,28 +1352,22 @@ static void launch_classify(const DevTableSet& T, const Tuning& tu, int t, const
         // next to the histogram, else without the records (the kernel then reads them from the
         // cross array: lrec cleared), else the base image (STAGE 1), else the image is read from
         // HBM / L2
+        // (+ 16: counters in an LDS histogram of every slot, k_classify FULLH; + 256: in 16-bit
+        // cells; + 32: the set has no PAIR tables, NOPAIR; + 64: the uniform cross layout, UNIF;
+        // + 128: its wide class records, WIDE)
         DevTableSet Tn = T;
-        const uint32_t all = T.node.img_words, norec = T.node.lrec ? T.node.lrec : all;
-        auto fits = [&](uint32_t w) {
-            return hist + (size_t)w * 4 <= tu.node_common_lds_max && w <= tu.node_stage_max_words + kCommonStageExtraWords;
-        };
-        // (+ 16: counters in an LDS histogram of every slot, k_classify FULLH)
-        const bool full = PG_NODE_FULLH && COUNT && T.n_slots <= kLdsHistMax - 2u;
-        // (+ 32: the set has no PAIR tables, k_classify NOPAIR)
-        const bool nopair = T.node.n_pair == 0 && PG_NODE_NOPAIR;
-        // (+ 64: the uniform cross layout, k_classify UNIF)
-        const bool unif = T.node.uniform != 0;  // (no PAIR tables either; its tries take the aligned encoding)
-        const bool wide = unif && T.node.wide != 0;  // (+ 128: its wide class records, k_classify WIDE)
+        if (!np.records_staged) Tn.node.lrec = 0;
+        const uint32_t code = np.stage_code;
         auto go1 = [&](auto stage, const DevTableSet& Ts, uint32_t words) {
             constexpr int S = decltype(stage)::value;
             if constexpr (COUNT) {
                 if constexpr ((S & 64) != 0 && PG_NODE_HALF) {
-                    if (full && half)
+                    if (code & 256)
                         return launch_one<MODE, COUNT, VEC, S + 16 + 256, true>(Ts, tu, t, src, dst, sport, dport, proto,
                                                                                 n, out, counters, st, hist, cells, words,
                                                                                 items);
                 }
-                if (full)
+                if (code & 16)
                     return launch_one<MODE, COUNT, VEC, S + 16, true>(Ts, tu, t, src, dst, sport, dport, proto, n, out,
                                                                       counters, st, hist, cells, words, items);
             }
@@ -1400,23 +1376,14 @@ static void launch_classify(const DevTableSet& T, const Tuning& tu, int t, const
         };
         auto go = [&](auto stage, const DevTableSet& Ts, uint32_t words) {
             constexpr int S = decltype(stage)::value;
-            if (wide) return go1(std::integral_constant<int, S + 96 + 128>{}, Ts, words);
-            if (unif) return go1(std::integral_constant<int, S + 96>{}, Ts, words);
-            if (nopair) return go1(std::integral_constant<int, S + 32>{}, Ts, words);
+            if (code & 128) return go1(std::integral_constant<int, S + 96 + 128>{}, Ts, words);
+            if (code & 64) return go1(std::integral_constant<int, S + 96>{}, Ts, words);
+            if (code & 32) return go1(std::integral_constant<int, S + 32>{}, Ts, words);
             go1(stage, Ts, words);
         };
-        if (T.node.cmap && (fits(all) || fits(norec))) {
-            const uint32_t w = fits(all) ? all : norec;
-            if (w < all) Tn.node.lrec = 0;
-            go(std::integral_constant<int, 3>{}, Tn, w);
-        } else if (T.node.img_words_base <= tu.node_stage_max_words) {
-            // (without a common-row section the records follow the base image directly)
-            const bool recs = !T.node.cmap && T.node.lrec && all <= tu.node_stage_max_words;
-            if (!recs) Tn.node.lrec = 0;
-            go(std::integral_constant<int, 1>{}, Tn, recs ? all : T.node.img_words_base);
-        } else {
-            go(std::integral_constant<int, 0>{}, T, 0u);
-        }
+        if ((code & 7u) == 3u) go(std::integral_constant<int, 3>{}, Tn, np.stage_words);
+        else if ((code & 7u) == 1u) go(std::integral_constant<int, 1>{}, Tn, np.stage_words);
+        else go(std::integral_constant<int, 0>{}, Tn, 0u);
     } else {
         launch_one<MODE, COUNT, VEC, 0, false>(T, tu, t, src, dst, sport, dport, proto, n, out, counters, st, hist,
                                                cells, 0, items);

@@ -291,6 +291,85 @@ inline LaunchPlan single_launch_plan(const DevTable& hd, uint32_t words, uint32_
     return p;
 }
 
+// The launch a PERPOD / CONN classify makes of the table set: the path, the k_classify STAGE of
+// the node kernel family, what of the node image is staged in LDS and the hit-counter scheme
+// (device.hip launch_classify<1|2> dispatches on it; pg_debug_node_launch_plan reports it to
+// tests). Host only, no HIP types.
+//   path            1 = the node classifier, 0 = the per-table path (node_path = 0, or no image)
+//   stage_code      the full k_classify STAGE: 3 = the image with its common-row section in LDS, 1 =
+//                   the base image in LDS, 0 = the image read from HBM / L2; + 32 no PAIR tables,
+//                   + 96 the uniform cross layout, + 96 + 128 with wide records; + 16 counters
+//                   in an LDS histogram of every slot, + 16 + 256 in 16-bit cells (per-table: 0)
+//   stage_words     image words copied into LDS
+//   records_staged  DevNode lrec is kept: the dst records are read from the image (STAGE 0: in
+//                   HBM) -- else the launch clears lrec and they are read from the cross array
+//   hist_kind       kHist*: none (no counters); every slot in 32-bit LDS cells (hist_cells slots +
+//                   2 cells); every slot in 16-bit cells (two per word + 1 word); the node's LDS
+//                   slot cache (hist_cells {key, count} cells + the hot cell); global atomics only;
+//                   per-table path over more than kLdsHistCells slots: the first hist_cells slots
+//   defers_any      a k_node_any launch follows (ANY-protocol packets of a uniform node)
+constexpr uint32_t kCommonStageExtraWords = 8192;  // the common-row section may take the image past node_stage_max_words
+enum : uint32_t { kHistNone = 0, kHistFull32, kHistHalf16, kHistCache, kHistGlobal, kHistWindow };
+struct NodeLaunchPlan {
+    uint32_t path, stage_code, stage_words, records_staged, hist_kind, hist_cells, hist_bytes, defers_any;
+};
+// the library's build-time choices the plan depends on (dev_node_build below): PG_NODE_FULLH,
+// PG_NODE_HALF, PG_NODE_NOPAIR, PG_CONN_DEFER_ANY, PG_POD_DEFER_ANY
+struct NodeBuild {
+    bool fullh, half, nopair, conn_defer_any, pod_defer_any;
+};
+// nd: the node's header fields, img non-null when the node was built (pointers not dereferenced)
+inline NodeLaunchPlan node_launch_plan(const DevNode& nd, uint32_t n_slots, int mode, bool count, const Tuning& tu,
+                                       const NodeBuild& b) {
+    NodeLaunchPlan p{};
+    const bool node = mode != 0 && tu.node_path && nd.img;
+    const bool small = n_slots <= kLdsHistCells;  // every slot fits the LDS histogram
+    // 16-bit cells: the uniform layout, every slot in the histogram, and a 32-bit histogram that
+    // even beside the base image would exceed the LDS budget of two workgroups per CU
+    const bool half = b.half && count && node && b.fullh && nd.uniform && small &&
+                      ((size_t)n_slots + 2u) * 4 + (size_t)nd.img_words_base * 4 > tu.node_common_lds_max;
+    if (count) {
+        if (half) p.hist_kind = kHistHalf16, p.hist_cells = n_slots, p.hist_bytes = ((n_slots + 1u) / 2u + 1u) * 4u;
+        else if (small) p.hist_kind = kHistFull32, p.hist_cells = n_slots, p.hist_bytes = (n_slots + 2u) * 4u;
+        else if (!node) {
+            p.hist_kind = kHistWindow;
+            p.hist_cells = tu.hist_window < kLdsHistCells ? tu.hist_window : kLdsHistCells;
+            p.hist_bytes = (p.hist_cells + 2u) * 4u;
+        } else if (tu.node_hist_cells >= 16u) {  // 2^k cells of {key, count} + the hot cell
+            p.hist_kind = kHistCache;
+            p.hist_cells = 1u << (31 - __builtin_clz(tu.node_hist_cells));
+            p.hist_bytes = (p.hist_cells + 1u) * 8u;
+        } else p.hist_kind = kHistGlobal;
+    }
+    if (!node) return p;
+    p.path = 1;
+    const uint32_t all = nd.img_words, norec = nd.lrec ? nd.lrec : all;
+    auto fits = [&](uint32_t w) {
+        return (size_t)p.hist_bytes + (size_t)w * 4 <= tu.node_common_lds_max &&
+               w <= tu.node_stage_max_words + kCommonStageExtraWords;
+    };
+    if (nd.cmap && (fits(all) || fits(norec))) {
+        // with the dst records when that fits the LDS budget next to the histogram, else without
+        p.stage_code = 3, p.stage_words = fits(all) ? all : norec;
+        p.records_staged = nd.lrec != 0 && p.stage_words == all;
+    } else if (nd.img_words_base <= tu.node_stage_max_words) {
+        // (without a common-row section the records follow the base image directly)
+        const bool recs = !nd.cmap && nd.lrec && all <= tu.node_stage_max_words;
+        p.stage_code = 1, p.stage_words = recs ? all : nd.img_words_base;
+        p.records_staged = recs;
+    } else {
+        p.records_staged = nd.lrec != 0;
+    }
+    const bool unif = nd.uniform != 0;  // (no PAIR tables either; its tries take the aligned encoding)
+    if (unif && nd.wide) p.stage_code += 96 + 128;
+    else if (unif) p.stage_code += 96;
+    else if (nd.n_pair == 0 && b.nopair) p.stage_code += 32;
+    if (half) p.stage_code += 16 + 256;
+    else if (b.fullh && count && small) p.stage_code += 16;
+    p.defers_any = unif && (mode == 2 ? b.conn_defer_any : b.pod_defer_any);
+    return p;
+}
+
 // key -> field; 0 ok, -1 unknown key or value out of range. *compiler: the key changes how
 // tables are compiled (the context recompiles on its next use).
 int tuning_set(Tuning& t, const std::string& key, int value, bool* compiler = nullptr);
@@ -351,6 +430,8 @@ const DevTableSet& dev_view(const DeviceBuffers* b);
 // the build's PG_CANDI_LEAN (device.hip: SINGLE over a CANDI table with its root staged takes the
 // dedicated walk, STAGE 6) -- what single_launch_plan is given, by the launch and by tests alike
 bool dev_candi_lean();
+// the build's node-launch choices node_launch_plan is given, by the launch and by tests alike
+NodeBuild dev_node_build();
 int dev_classify(const DevTableSet& T, const Tuning& tu, int mode, int table_id, const uint32_t* src,
                  const uint32_t* dst, const uint16_t* sport, const uint16_t* dport, const uint8_t* proto, uint64_t n,
                  uint32_t* out, unsigned long long* counters, void* stream, std::string* err);

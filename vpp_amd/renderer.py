@@ -326,6 +326,19 @@ class Engine:
         self._ck(lib.pg_debug_launch_plan(self.h, table_id, int(counters), C.byref(st), C.byref(sw), C.byref(hc)))
         return {"stage": st.value, "stage_words": sw.value, "hist_cells": hc.value}
 
+    HIST_KINDS = ("none", "full32", "half16", "cache", "global", "window")
+
+    def debug_node_launch_plan(self, mode, counters=False):
+        """TESTS ONLY: the launch a PERPOD / CONN classify makes under this context's knobs
+        (pg_debug_node_launch_plan) -> {path: "node" | "per-table", stage: the full k_classify STAGE
+        code, stage_words, records_staged, hist_kind (HIST_KINDS), hist_cells, hist_bytes,
+        defers_any}"""
+        p = _capi.pg_node_launch_plan()
+        self._ck(lib.pg_debug_node_launch_plan(self.h, mode, int(counters), C.byref(p)))
+        return {"path": "node" if p.path else "per-table", "stage": p.stage_code, "stage_words": p.stage_words,
+                "records_staged": bool(p.records_staged), "hist_kind": self.HIST_KINDS[p.hist_kind],
+                "hist_cells": p.hist_cells, "hist_bytes": p.hist_bytes, "defers_any": bool(p.defers_any)}
+
     def node_stats(self):
         """node classifier size {ip_classes, key_classes, image_bytes, cross_bytes}, or None."""
         a, b = C.c_uint32(), C.c_uint32()
