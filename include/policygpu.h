@@ -260,6 +260,8 @@ int pg_debug_walk_blob(pg_ctx* ctx, const char* acl_name, const uint32_t* src, c
  * Does not touch the device. */
 int pg_debug_classify_host(pg_ctx* ctx, int mode, int table_id, const pg_tuple_soa* tuples, uint64_t n,
                            uint32_t* out, uint64_t* counters, int flags);
+/* TESTS ONLY, the same for the reachability matrix: pg_debug_reach_matrix_host, declared with
+ * pg_reach_matrix below. */
 /* TESTS ONLY -- never on the classify path: install n host counters (e.g. from
  * pg_debug_classify_host) as the LOCAL or CLUSTER snapshot in the currently compiled slot layout,
  * so the snapshot readers below can be tested without a GPU. n must equal the slot count. */
@@ -447,6 +449,46 @@ typedef struct pg_conn_query {
 } pg_conn_query;
 /* out[i] = ConnAction; out_slot (optional) = deciding slot per query */
 int pg_connections(pg_ctx* ctx, const pg_conn_query* q, size_t n, int32_t* out, uint32_t* out_slot);
+
+/* ---- reachability matrix: testConnection over src x dst x service on the device -------
+ * "Which end points can reach which, on which services?" after a policy commit. Pair (service
+ * v, src i, dst j) gets exactly the verdict word pg_classify(PG_MODE_CONN) gives the tuple
+ * (src_ip[i], dst_ip[j], services[v].src_port, services[v].dst_port, services[v].protocol): end
+ * points are resolved from the addresses (a pod of this node, a remote pod, a non-pod address),
+ * with the same preamble FAILUREs and "unresolved" slot; the deciding slot is the slot of the
+ * last evaluation. What depends on one end point or one service alone (trie walks, iphash
+ * probes) is computed once per end point / service, not once per pair.
+ *   out_packed  device, n_svc * n_src * pg_reach_row_words(n_dst) words: the ConnAction of (v, i,
+ *               j) in bits [2 * (j & 15), 2 * (j & 15) + 1] of word (v * n_src + i) * row_words +
+ *               (j >> 4); the padding bits of a row's last word are zero
+ *   out_words   device, optional: n_svc * n_src * n_dst full verdict words, row-major (drill-down
+ *               to the deciding rule with pg_slot_info)
+ * The call is an audit, not traffic: it never touches the hit counters or their snapshots.
+ * Like pg_gen_tuples it compiles and uploads stale tables first, copies the small host arrays
+ * in, enqueues its kernels in order on hip_stream and may synchronise that stream before it
+ * returns. A zero n_src, n_dst or n_svc: PG_OK, nothing written. PG_EINVAL: null spec or
+ * out_packed, a side longer than 2^20, more than 4096 services. IPv4 only. */
+typedef struct pg_service {
+    int32_t protocol;         /* PG_PROTO_*; codes > 3 behave as in pg_classify (ANY) */
+    uint16_t src_port, dst_port;
+} pg_service;
+typedef struct pg_reach_spec {
+    const uint32_t* src_ip;   /* host arrays, host-order IPv4; duplicates allowed */
+    size_t n_src;
+    const uint32_t* dst_ip;
+    size_t n_dst;
+    const pg_service* services;
+    size_t n_svc;
+} pg_reach_spec;
+size_t pg_reach_row_words(size_t n_dst); /* (n_dst + 15) / 16 */
+int pg_reach_matrix(pg_ctx* ctx, const pg_reach_spec* spec, uint32_t* out_packed, uint32_t* out_words,
+                    void* hip_stream);
+/* TESTS ONLY -- never on the audit path: pg_reach_matrix's per-end-point, per-service and
+ * per-pair code (reach.hpp, the same templates the kernels instantiate) run on the host with
+ * host output arrays. flags: bit 0 = the node classifier when it exists and is uniform (else the
+ * per-table path), as in pg_debug_classify_host. Does not touch the device. */
+int pg_debug_reach_matrix_host(pg_ctx* ctx, const pg_reach_spec* spec, uint32_t* out_packed, uint32_t* out_words,
+                               int flags);
 
 /* ---- policy configurator ------------------------------------------
  * configurator.PolicyConfiguratorAPI / Txn (plugins/policy/configurator/configurator_api.go:28-54,

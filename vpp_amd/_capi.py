@@ -82,6 +82,15 @@ class pg_conn_query(C.Structure):
                 ("dst_ip", C.c_char_p), ("protocol", C.c_int32), ("src_port", C.c_uint16), ("dst_port", C.c_uint16)]
 
 
+class pg_service(C.Structure):
+    _fields_ = [("protocol", C.c_int32), ("src_port", C.c_uint16), ("dst_port", C.c_uint16)]
+
+
+class pg_reach_spec(C.Structure):
+    _fields_ = [("src_ip", C.c_void_p), ("n_src", C.c_size_t), ("dst_ip", C.c_void_p), ("n_dst", C.c_size_t),
+                ("services", C.POINTER(pg_service)), ("n_svc", C.c_size_t)]
+
+
 class pg_pod_id(C.Structure):
     _fields_ = [("ns", C.c_char_p), ("name", C.c_char_p)]
 
@@ -223,6 +232,9 @@ _SIGS = {
     "pg_gen_tuples": (C.c_int, [_P, C.POINTER(pg_gen_spec), C.c_uint64, _P, _P, _P, _P, _P, _P]),
     "pg_connections": (C.c_int, [_P, C.POINTER(pg_conn_query), C.c_size_t, C.POINTER(C.c_int32),
                                  C.POINTER(C.c_uint32)]),
+    "pg_reach_row_words": (C.c_size_t, [C.c_size_t]),
+    "pg_reach_matrix": (C.c_int, [_P, C.POINTER(pg_reach_spec), _P, _P, _P]),
+    "pg_debug_reach_matrix_host": (C.c_int, [_P, C.POINTER(pg_reach_spec), _P, _P, C.c_int]),
     "pg_session_rules_new": (_P, [C.c_char_p]),
     "pg_session_rules_free": (None, [_P]),
     "pg_session_rules_clear": (C.c_int, [_P]),

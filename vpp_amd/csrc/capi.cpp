@@ -8,6 +8,7 @@
 
 #include "capi_internal.hpp"
 #include "classify.hpp"
+#include "reach.hpp"
 
 using namespace pg;
 
@@ -1322,6 +1323,118 @@ int pg_connections(pg_ctx* ctx, const pg_conn_query* q, size_t n, int32_t* out, 
         uint32_t w = res[where[i]];
         out[i] = (int32_t)(w >> 30);
         if (out_slot) out_slot[i] = w & 0x3FFFFFFFu;
+    }
+    return PG_OK;
+    GUARD_END(ctx)
+}
+
+}  // extern "C"
+
+// ---- reachability matrix (reach.hpp) -------------------------------------------------------------
+namespace {
+// argument checks shared by pg_reach_matrix and its host twin: PG_OK with *empty set when there
+// is nothing to do
+int reach_args(pg_ctx* ctx, const pg_reach_spec* spec, const uint32_t* out_packed, bool* empty) {
+    if (!ctx || !spec || !out_packed) return PG_EINVAL;
+    if (spec->n_src > kReachMaxSide || spec->n_dst > kReachMaxSide) return fail(ctx, PG_EINVAL, "a side longer than 2^20");
+    if (spec->n_svc > kReachMaxSvc) return fail(ctx, PG_EINVAL, "more than 4096 services");
+    *empty = !spec->n_src || !spec->n_dst || !spec->n_svc;
+    if (!*empty && (!spec->src_ip || !spec->dst_ip || !spec->services)) return fail(ctx, PG_EINVAL, "null spec array");
+    return PG_OK;
+}
+std::vector<W4> reach_services(const pg_reach_spec* spec) {
+    std::vector<W4> v(spec->n_svc);
+    for (size_t k = 0; k < spec->n_svc; k++)
+        v[k] = reach_service(spec->services[k].protocol, spec->services[k].src_port, spec->services[k].dst_port);
+    return v;
+}
+
+// every word of the services `list` (one form's), as k_reach_pairs runs them
+template <bool UNI, bool WIDE>
+void host_reach_pairs(const DevTableSet& T, const ReachPass& P) {
+    const uint64_t rw = reach_row_words(P.n_dst);
+    const DevLoader img{T.node.img};
+    for (uint32_t k = 0; k < P.n_list; k++) {
+        const uint32_t v = P.svc_list[k];
+        for (uint32_t i = 0; i < P.n_src; i++) {
+            const uint64_t row = (uint64_t)v * P.n_src + i;
+            for (uint64_t jw = 0; jw < rw; jw++) {
+                const uint32_t j0 = (uint32_t)jw * kReachWordPairs;
+                uint32_t* ow = P.out_words ? P.out_words + row * P.n_dst + j0 : nullptr;
+                auto emit = [&](uint32_t r, const uint32_t(&o)[kReachQ], uint32_t valid) {
+                    for (uint32_t q = 0; ow && q < valid; q++) ow[r * kReachQ + q] = o[q];
+                };
+                uint32_t packed;
+                if constexpr (UNI)
+                    packed = reach_word_uni<WIDE>(T, T.node, img, P.rec_s[i], P.cls_s[i], P.rec_d, P.cls_d, j0, P.n_dst,
+                                                  P.svc[v], emit);
+                else
+                    packed = reach_word_tab(T, P.rec_s[i], P.rec_d, j0, P.n_dst, P.svc[v], emit);
+                P.out_packed[row * rw + jw] = packed;
+            }
+        }
+    }
+}
+}  // namespace
+
+extern "C" {
+
+size_t pg_reach_row_words(size_t n_dst) { return (size_t)reach_row_words(n_dst); }
+
+int pg_reach_matrix(pg_ctx* ctx, const pg_reach_spec* spec, uint32_t* out_packed, uint32_t* out_words,
+                    void* stream) {
+    bool empty = false;
+    if (int rc = reach_args(ctx, spec, out_packed, &empty)) return rc;
+    if (empty) return PG_OK;
+    DEVICE_GUARD(ctx);
+    GUARD_BEGIN
+    int rc = ctx->eng.sync();
+    if (rc) return rc;
+    const DevTableSet& T = *ctx->eng.view();
+    const std::vector<W4> svc = reach_services(spec);
+    const ReachSpecDev sd{spec->src_ip, spec->dst_ip, svc.data(), (uint32_t)spec->n_src, (uint32_t)spec->n_dst,
+                          (uint32_t)spec->n_svc};
+    std::string err;
+    if (dev_reach_matrix(T, ctx->eng.tune, sd, out_packed, out_words, stream, &err) != 0 ||
+        dev_mark_use(ctx->eng.cur, stream, false, &err) != 0)
+        return fail(ctx, PG_EIO, err);
+    return PG_OK;
+    GUARD_END(ctx)
+}
+
+int pg_debug_reach_matrix_host(pg_ctx* ctx, const pg_reach_spec* spec, uint32_t* out_packed, uint32_t* out_words,
+                               int flags) {
+    bool empty = false;
+    if (int rc = reach_args(ctx, spec, out_packed, &empty)) return rc;
+    GUARD_BEGIN
+    if (empty) return PG_OK;
+    Engine& E = ctx->eng;
+    if (!E.compiled) E.compile();
+    const DevTableSet T = host_view(E.host);
+    const uint32_t ns = (uint32_t)spec->n_src, nd = (uint32_t)spec->n_dst, nv = (uint32_t)spec->n_svc, ne = ns + nd;
+    const std::vector<W4> svc = reach_services(spec);
+    const bool form_a = (flags & 1) && reach_form_a(T.node, E.tune);
+    std::vector<uint32_t> la, lb;  // the services of each form
+    for (uint32_t v = 0; v < nv; v++) (form_a && svc[v].x <= 2u ? la : lb).push_back(v);
+    auto ip_of = [&](uint32_t e) { return e < ns ? spec->src_ip[e] : spec->dst_ip[e - ns]; };
+    std::vector<W4> rec(ne);
+    std::vector<uint32_t> cls(ne);
+    std::vector<W2> g(nv);
+    if (!la.empty()) {
+        const DevLoader img{T.node.img};
+        for (uint32_t e = 0; e < ne; e++) reach_end_uni(T.node, img, ip_of(e), &rec[e], &cls[e]);
+        for (uint32_t v : la) g[v] = reach_svc_uni(T.node, img, svc[v]);
+        const ReachPass P{rec.data(), rec.data() + ns, cls.data(), cls.data() + ns, g.data(), la.data(),
+                          (uint32_t)la.size(), ns, nd, out_packed, out_words};
+        if (T.node.wide) host_reach_pairs<true, true>(T, P);
+        else host_reach_pairs<true, false>(T, P);
+    }
+    if (!lb.empty()) {
+        for (uint32_t e = 0; e < ne; e++) rec[e] = reach_end_tab(T, ip_of(e));
+        for (uint32_t v : lb) g[v] = reach_svc_tab(svc[v]);
+        const ReachPass P{rec.data(), rec.data() + ns, nullptr, nullptr, g.data(), lb.data(), (uint32_t)lb.size(), ns, nd,
+                          out_packed, out_words};
+        host_reach_pairs<false, false>(T, P);
     }
     return PG_OK;
     GUARD_END(ctx)

@@ -196,6 +196,49 @@ def allreduce_counters_all(engines):
     return [counters_snapshot(e) for e in engines]
 
 
+# ---- reachability matrix (include/policygpu.h pg_reach_matrix) -------------------------------
+def reach_spec(src_ips, dst_ips, services):
+    """pg_reach_spec over host arrays: IPv4 addresses as u32, services as (protocol, src port, dst
+    port) -> (spec, the arrays it points into: keep them alive for the call)"""
+    src = np.ascontiguousarray(src_ips, dtype=np.uint32)
+    dst = np.ascontiguousarray(dst_ips, dtype=np.uint32)
+    svc = (_capi.pg_service * max(1, len(services)))()
+    for i, (proto, sport, dport) in enumerate(services):
+        svc[i].protocol, svc[i].src_port, svc[i].dst_port = int(proto), int(sport), int(dport)
+    spec = _capi.pg_reach_spec(src.ctypes.data, len(src), dst.ctypes.data, len(dst), svc, len(services))
+    return spec, (src, dst, svc)
+
+
+def reach_row_words(n_dst):
+    return lib.pg_reach_row_words(n_dst)
+
+
+def reach_matrix(engine, src_ips, dst_ips, services, words=False, stream=None):
+    """testConnection of every (service, src, dst) on the GPU (pg_reach_matrix) -> the packed
+    ConnActions, an int32 tensor [n_svc, n_src, row_words] (2 bits per pair, unpack_reach), and with
+    ``words`` also the full verdict words, an int32 tensor [n_svc, n_src, n_dst]. The call never
+    touches the hit counters."""
+    spec, keep = reach_spec(src_ips, dst_ips, services)
+    n_svc, n_src, n_dst = len(services), spec.n_src, spec.n_dst
+    packed = torch.empty((n_svc, n_src, reach_row_words(n_dst)), dtype=torch.int32, device="cuda")
+    full = torch.empty((n_svc, n_src, n_dst), dtype=torch.int32, device="cuda") if words else None
+    if packed.numel() == 0:  # (an empty tensor has no address to hand over; the call would write nothing)
+        return (packed, full) if words else packed
+    engine._ck(lib.pg_reach_matrix(engine.h, C.byref(spec), packed.data_ptr(), full.data_ptr() if words else None,
+                                   _stream_ptr(stream)))
+    del keep
+    return (packed, full) if words else packed
+
+
+def unpack_reach(packed, n_svc, n_src, n_dst):
+    """packed reachability words (tensor or array) -> uint8 ConnActions [n_svc, n_src, n_dst]"""
+    if isinstance(packed, torch.Tensor):
+        packed = packed.cpu().numpy()
+    w = np.ascontiguousarray(packed).view(np.uint32).reshape(n_svc, n_src, reach_row_words(n_dst))
+    codes = (w[..., None] >> (2 * np.arange(16, dtype=np.uint32))) & 3
+    return codes.reshape(n_svc, n_src, 16 * w.shape[2])[..., :n_dst].astype(np.uint8)
+
+
 def unpack(out_u32):
     w = out_u32.astype(np.uint32)
     return (w >> 30).astype(np.int64), (w & 0x3FFFFFFF).astype(np.int64)

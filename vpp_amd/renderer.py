@@ -304,6 +304,50 @@ class Engine:
                                             int(node) | (2 if pred else 0) | (4 if common else 0)))
         return (out, cnt) if counters else out
 
+    def debug_reach_matrix_host(self, src_ips, dst_ips, services, words=True, node=True):
+        """TESTS ONLY: pg_reach_matrix's code run on the host (pg_debug_reach_matrix_host).
+        services: (protocol, src port, dst port). -> packed u32 [n_svc, n_src, row_words], and the
+        full verdict words u32 [n_svc, n_src, n_dst] when ``words``."""
+        import numpy as np
+        src = np.ascontiguousarray(src_ips, dtype=np.uint32)
+        dst = np.ascontiguousarray(dst_ips, dtype=np.uint32)
+        svc = (_capi.pg_service * max(1, len(services)))()
+        for i, (proto, sport, dport) in enumerate(services):
+            svc[i].protocol, svc[i].src_port, svc[i].dst_port = int(proto), int(sport), int(dport)
+        spec = _capi.pg_reach_spec(src.ctypes.data, len(src), dst.ctypes.data, len(dst), svc, len(services))
+        rw = lib.pg_reach_row_words(len(dst))
+        packed = np.full((len(services), len(src), rw), 0xFFFFFFFF, np.uint32)
+        full = np.full((len(services), len(src), len(dst)), 0xFFFFFFFF, np.uint32) if words else None
+        p = lambda x: x.ctypes.data_as(C.c_void_p)
+        self._ck(lib.pg_debug_reach_matrix_host(self.h, C.byref(spec), p(packed), p(full) if words else None,
+                                                int(node)))
+        return (packed, full) if words else packed
+
+    def _pod_ips(self, pods):
+        """registered IPv4 addresses of "ns/name" pods as u32"""
+        out = []
+        for pod in pods:
+            key = "%s/%s" % _pod(pod)
+            if key not in self.registered_pods:
+                raise PolicyError(_capi.PG_ENOENT, "pod %s is not registered" % key)
+            out.append(int(ipaddress.IPv4Address(self.registered_pods[key][0])))
+        return out
+
+    def reachability(self, src_pods, dst_pods, services, host=False):
+        """Which pods reach which, on which services: the ConnAction of every (service, src pod,
+        dst pod), a uint8 array [n_svc, n_src, n_dst], by one pg_reach_matrix call. Pods are
+        "ns/name" (or (ns, name)), resolved through the addresses given to RegisterPod; services
+        are (protocol, src port, dst port). ``host``: TESTS ONLY, the host twin instead of the GPU."""
+        from . import device as D
+        src, dst = self._pod_ips(src_pods), self._pod_ips(dst_pods)
+        if host:
+            packed = self.debug_reach_matrix_host(src, dst, services, words=False)
+        else:
+            import torch
+            packed = D.reach_matrix(self, src, dst, services)
+            torch.cuda.synchronize()
+        return D.unpack_reach(packed, len(services), len(src), len(dst))
+
     def debug_walk_stats(self, table_id, src, dst, dport, proto):
         """MEASUREMENT: per tuple, the loads a SINGLE launch on table_id makes of the table's
         structure (pg_debug_walk_stats) -> (lds_reads u32[n], mem_reads u32[n], launch STAGE)"""
