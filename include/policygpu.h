@@ -490,6 +490,58 @@ int pg_reach_matrix(pg_ctx* ctx, const pg_reach_spec* spec, uint32_t* out_packed
 int pg_debug_reach_matrix_host(pg_ctx* ctx, const pg_reach_spec* spec, uint32_t* out_packed, uint32_t* out_words,
                                int flags);
 
+/* ---- port sweep: the open dst ports of every src x dst pair on the device ----------------
+ * "Between these end points, which ports are open?" For a fixed protocol (TCP or UDP) and src
+ * port, evalACL tests a packet's dst port only against the rules' dst-port ranges, so the verdict
+ * of (src, dst, protocol, src_port, dst_port) is constant inside every elementary interval that
+ * the rules' dst-port bounds cut 0..65535 into. A sweep over all 65,536 ports is K evaluations
+ * per pair -- tens to hundreds on a real table set.
+ *
+ * pg_port_intervals: the elementary dst-port intervals of a protocol (PG_PROTO_TCP or
+ * PG_PROTO_UDP) over every installed ACL: lo[0] = 0 < lo[1] < ... ascending; interval k =
+ * [lo[k], lo[k+1] - 1], the last ends at 65535. Returns K (>= 1; 1 without ACLs), copies
+ * min(K, cap) bounds (lo may be null when cap is 0). Two ports of one interval get the same
+ * (action, rule index) from evalACL in every installed ACL, for every src / dst. Every lo[k], k >
+ * 0, is lower & 0xFFFF or (upper & 0xFFFF) + 1 of the dst range of some installed rule's L4
+ * section of that protocol -- the bounds as evalACL compares them, after its uint16 truncation --
+ * so K <= 2 * rules + 1; rules that can never match still cut. Host only, no device work.
+ * PG_EINVAL: another protocol. */
+int pg_port_intervals(pg_ctx* ctx, int protocol, uint32_t* lo, size_t cap);
+/* pg_reach_ports: with K and lo[] of pg_port_intervals(protocol) and row_words =
+ * pg_reach_row_words(K),
+ *   out_codes  device, required, n_src * n_dst * row_words words: the ConnAction of pair (i, j) on
+ *              interval k in bits [2 * (k & 15), 2 * (k & 15) + 1] of word (i * n_dst + j) *
+ *              row_words + (k >> 4); the padding bits of a pair's last word are zero
+ *   out_open   device, optional, n_src * n_dst words: per pair the number of dst ports whose
+ *              ConnAction is PG_CONN_ALLOW (the lengths of its ALLOW intervals), 0..65536
+ *   out_words  device, optional, n_src * n_dst * K words: the full verdict word of every (pair,
+ *              interval), bit-identical to pg_classify(PG_MODE_CONN) on (src_ip[i], dst_ip[j],
+ *              src_port, lo[k], protocol)
+ * End-point resolution, preamble FAILUREs, the "unresolved" slot and the slot reported (that of
+ * the last evaluation) are pg_reach_matrix's. The call never touches the hit counters or their
+ * snapshots. Like pg_reach_matrix it compiles and uploads stale tables first, enqueues in order
+ * on hip_stream and may synchronise it. An empty side: PG_OK, nothing written. PG_EINVAL: a null
+ * spec or out_codes; a protocol other than TCP / UDP; a side longer than 2^20; n_src * n_dst *
+ * row_words >= 2^32; n_intervals different from the partition's current K (the ACLs changed
+ * since pg_port_intervals; pg_last_error says so). */
+typedef struct pg_port_sweep_spec {
+    const uint32_t* src_ip;   /* host arrays, host-order IPv4; duplicates allowed */
+    size_t n_src;
+    const uint32_t* dst_ip;
+    size_t n_dst;
+    int32_t protocol;         /* PG_PROTO_TCP | PG_PROTO_UDP */
+    uint16_t src_port;        /* fixed: the SYN-ACK key */
+    uint16_t _pad;
+    size_t n_intervals;       /* K the caller sized its buffers for */
+} pg_port_sweep_spec;
+int pg_reach_ports(pg_ctx* ctx, const pg_port_sweep_spec* spec, uint32_t* out_codes, uint32_t* out_open,
+                   uint32_t* out_words, void* hip_stream);
+/* TESTS ONLY -- never on the audit path: pg_reach_ports's per-pair code (ports.hpp, the same
+ * templates the kernel instantiates) on the host with host output arrays. flags: bit 0 as in
+ * pg_debug_reach_matrix_host. Does not touch the device. */
+int pg_debug_reach_ports_host(pg_ctx* ctx, const pg_port_sweep_spec* spec, uint32_t* out_codes, uint32_t* out_open,
+                              uint32_t* out_words, int flags);
+
 /* ---- policy configurator ------------------------------------------
  * configurator.PolicyConfiguratorAPI / Txn (plugins/policy/configurator/configurator_api.go:28-54,
  * configurator_impl.go:104-472): K8s-shaped policies per pod -> ordered ContivRule lists

@@ -91,6 +91,11 @@ class pg_reach_spec(C.Structure):
                 ("services", C.POINTER(pg_service)), ("n_svc", C.c_size_t)]
 
 
+class pg_port_sweep_spec(C.Structure):
+    _fields_ = [("src_ip", C.c_void_p), ("n_src", C.c_size_t), ("dst_ip", C.c_void_p), ("n_dst", C.c_size_t),
+                ("protocol", C.c_int32), ("src_port", C.c_uint16), ("_pad", C.c_uint16), ("n_intervals", C.c_size_t)]
+
+
 class pg_pod_id(C.Structure):
     _fields_ = [("ns", C.c_char_p), ("name", C.c_char_p)]
 
@@ -235,6 +240,9 @@ _SIGS = {
     "pg_reach_row_words": (C.c_size_t, [C.c_size_t]),
     "pg_reach_matrix": (C.c_int, [_P, C.POINTER(pg_reach_spec), _P, _P, _P]),
     "pg_debug_reach_matrix_host": (C.c_int, [_P, C.POINTER(pg_reach_spec), _P, _P, C.c_int]),
+    "pg_port_intervals": (C.c_int, [_P, C.c_int, _P, C.c_size_t]),
+    "pg_reach_ports": (C.c_int, [_P, C.POINTER(pg_port_sweep_spec), _P, _P, _P, _P]),
+    "pg_debug_reach_ports_host": (C.c_int, [_P, C.POINTER(pg_port_sweep_spec), _P, _P, _P, C.c_int]),
     "pg_session_rules_new": (_P, [C.c_char_p]),
     "pg_session_rules_free": (None, [_P]),
     "pg_session_rules_clear": (C.c_int, [_P]),

@@ -8,6 +8,7 @@
 
 #include "capi_internal.hpp"
 #include "classify.hpp"
+#include "ports.hpp"
 #include "reach.hpp"
 
 using namespace pg;
@@ -1436,6 +1437,156 @@ int pg_debug_reach_matrix_host(pg_ctx* ctx, const pg_reach_spec* spec, uint32_t*
                           out_packed, out_words};
         host_reach_pairs<false, false>(T, P);
     }
+    return PG_OK;
+    GUARD_END(ctx)
+}
+
+}  // extern "C"
+
+// ---- port sweep (ports.hpp) ----------------------------------------------------------------------
+namespace {
+// The elementary dst-port intervals of a protocol: 0 and, of every installed rule whose L4 section
+// of that protocol carries a dst range, the two bounds as evalACL compares them (after its uint16
+// truncation, aclengine_mock.go:589): lower & 0xFFFF and (upper & 0xFFFF) + 1. Rules that never
+// reach the comparison (a structural FAILURE before it, an empty range) only add cuts. Both
+// protocols' bounds are kept with the engine until the next ACL change (Engine::touch).
+const std::vector<uint32_t>& port_bounds(Engine& E, int protocol) {
+    if (!E.port_lo_valid) {
+        for (int p : {PG_PROTO_TCP, PG_PROTO_UDP}) {
+            std::vector<uint32_t>& lo = E.port_lo[p];
+            lo.assign(1, 0u);
+            for (const auto& kv : E.by_name)
+                for (const AclRule& r : kv.second->rules) {
+                    const L4Section& s = p == PG_PROTO_TCP ? r.tcp : r.udp;
+                    if (!s.present || !s.has_dst) continue;
+                    lo.push_back(s.dst.lower & 0xFFFFu);
+                    lo.push_back((s.dst.upper & 0xFFFFu) + 1u);
+                }
+            std::sort(lo.begin(), lo.end());
+            lo.erase(std::unique(lo.begin(), lo.end()), lo.end());
+            if (lo.back() == 65536u) lo.pop_back();
+        }
+        E.port_lo_valid = true;
+    }
+    return E.port_lo[protocol];
+}
+
+// argument checks shared by pg_reach_ports and its host twin: PG_OK with *empty set when there is
+// nothing to do, else *lo = the partition the call runs on
+int ports_args(pg_ctx* ctx, const pg_port_sweep_spec* spec, const uint32_t* out_codes, bool* empty,
+               std::vector<uint32_t>* lo) {
+    if (!ctx || !spec || !out_codes) return PG_EINVAL;
+    if (spec->protocol != PG_PROTO_TCP && spec->protocol != PG_PROTO_UDP)
+        return fail(ctx, PG_EINVAL, "a port sweep takes PG_PROTO_TCP or PG_PROTO_UDP");
+    if (spec->n_src > kReachMaxSide || spec->n_dst > kReachMaxSide) return fail(ctx, PG_EINVAL, "a side longer than 2^20");
+    *lo = port_bounds(ctx->eng, spec->protocol);
+    if (spec->n_intervals != lo->size())
+        return fail(ctx, PG_EINVAL, "n_intervals is " + std::to_string(spec->n_intervals) + " but the installed ACLs give " +
+                                        std::to_string(lo->size()) + " intervals: they changed since pg_port_intervals");
+    // (both sides <= 2^20 and row words <= 4097: the product fits 64 bits)
+    if ((uint64_t)spec->n_src * spec->n_dst * reach_row_words(lo->size()) >> 32)
+        return fail(ctx, PG_EINVAL, "n_src * n_dst * row_words(K) reaches 2^32");
+    *empty = !spec->n_src || !spec->n_dst;
+    if (!*empty && (!spec->src_ip || !spec->dst_ip)) return fail(ctx, PG_EINVAL, "null spec array");
+    return PG_OK;
+}
+
+struct HostPorts {
+    const W4 *rec_s, *rec_d;
+    const uint32_t *cls_s, *cls_d;  // form A
+    const W2* iv;
+    const uint32_t* len;
+    uint32_t K, n_src, n_dst;
+    uint32_t *codes, *open, *words;
+};
+// every pair, as k_ports_pairs runs it
+template <bool UNI, bool WIDE>
+void host_ports_pairs(const DevTableSet& T, const HostPorts& P) {
+    const uint64_t rw = reach_row_words(P.K);
+    const DevLoader img{T.node.img};
+    for (uint32_t i = 0; i < P.n_src; i++)
+        for (uint32_t j = 0; j < P.n_dst; j++) {
+            const uint64_t p = (uint64_t)i * P.n_dst + j;
+            auto emit_code = [&](uint32_t w, uint32_t word) { P.codes[p * rw + w] = word; };
+            auto emit_words = [&](uint32_t k0, const uint32_t(&o)[kReachQ], uint32_t valid) {
+                for (uint32_t q = 0; P.words && q < valid; q++) P.words[p * P.K + k0 + q] = o[q];
+            };
+            uint32_t open;
+            if constexpr (UNI)
+                open = ports_pair_uni<WIDE>(T, T.node, img, P.rec_s[i], P.cls_s[i], P.rec_d[j], P.cls_d[j], P.iv, P.len,
+                                            P.K, emit_code, emit_words);
+            else
+                open = ports_pair_tab(T, P.rec_s[i], P.rec_d[j], P.iv, P.len, P.K, emit_code, emit_words);
+            if (P.open) P.open[p] = open;
+        }
+}
+}  // namespace
+
+extern "C" {
+
+int pg_port_intervals(pg_ctx* ctx, int protocol, uint32_t* lo, size_t cap) {
+    if (!ctx) return PG_EINVAL;
+    GUARD_BEGIN
+    if (protocol != PG_PROTO_TCP && protocol != PG_PROTO_UDP)
+        return fail(ctx, PG_EINVAL, "port intervals exist for PG_PROTO_TCP and PG_PROTO_UDP");
+    const std::vector<uint32_t>& b = port_bounds(ctx->eng, protocol);
+    if (lo) std::copy(b.begin(), b.begin() + std::min(cap, b.size()), lo);
+    return (int)b.size();
+    GUARD_END(ctx)
+}
+
+int pg_reach_ports(pg_ctx* ctx, const pg_port_sweep_spec* spec, uint32_t* out_codes, uint32_t* out_open,
+                   uint32_t* out_words, void* stream) {
+    GUARD_BEGIN
+    bool empty = false;
+    std::vector<uint32_t> lo;
+    if (int rc = ports_args(ctx, spec, out_codes, &empty, &lo)) return rc;
+    if (empty) return PG_OK;
+    DEVICE_GUARD(ctx);
+    int rc = ctx->eng.sync();
+    if (rc) return rc;
+    const DevTableSet& T = *ctx->eng.view();
+    const PortsSpecDev sd{spec->src_ip, spec->dst_ip, lo.data(), (uint32_t)spec->n_src, (uint32_t)spec->n_dst,
+                          (uint32_t)lo.size(), (uint32_t)spec->protocol, spec->src_port};
+    std::string err;
+    if (dev_reach_ports(T, ctx->eng.tune, sd, out_codes, out_open, out_words, stream, &err) != 0 ||
+        dev_mark_use(ctx->eng.cur, stream, false, &err) != 0)
+        return fail(ctx, PG_EIO, err);
+    return PG_OK;
+    GUARD_END(ctx)
+}
+
+int pg_debug_reach_ports_host(pg_ctx* ctx, const pg_port_sweep_spec* spec, uint32_t* out_codes, uint32_t* out_open,
+                              uint32_t* out_words, int flags) {
+    GUARD_BEGIN
+    bool empty = false;
+    std::vector<uint32_t> lo;
+    if (int rc = ports_args(ctx, spec, out_codes, &empty, &lo)) return rc;
+    if (empty) return PG_OK;
+    Engine& E = ctx->eng;
+    if (!E.compiled) E.compile();
+    const DevTableSet T = host_view(E.host);
+    const uint32_t ns = (uint32_t)spec->n_src, nd = (uint32_t)spec->n_dst, K = (uint32_t)lo.size(), ne = ns + nd;
+    const bool form_a = (flags & 1) && reach_form_a(T.node, E.tune);
+    auto ip_of = [&](uint32_t e) { return e < ns ? spec->src_ip[e] : spec->dst_ip[e - ns]; };
+    std::vector<W4> rec(ne);
+    std::vector<uint32_t> cls(ne), len(K);
+    std::vector<W2> iv(K);
+    const DevLoader img{T.node.img};
+    for (uint32_t e = 0; e < ne; e++) {
+        if (form_a) reach_end_uni(T.node, img, ip_of(e), &rec[e], &cls[e]);
+        else rec[e] = reach_end_tab(T, ip_of(e));
+    }
+    for (uint32_t k = 0; k < K; k++) {
+        const W4 s = reach_service(spec->protocol, spec->src_port, lo[k]);
+        iv[k] = form_a ? reach_svc_uni(T.node, img, s) : reach_svc_tab(s);
+        len[k] = ports_len(lo.data(), K, k);
+    }
+    const HostPorts P{rec.data(), rec.data() + ns, cls.data(), cls.data() + ns, iv.data(), len.data(), K, ns, nd,
+                      out_codes, out_open, out_words};
+    if (!form_a) host_ports_pairs<false, false>(T, P);
+    else if (T.node.wide) host_ports_pairs<true, true>(T, P);
+    else host_ports_pairs<true, false>(T, P);
     return PG_OK;
     GUARD_END(ctx)
 }

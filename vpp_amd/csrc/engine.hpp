@@ -111,7 +111,10 @@ struct Engine {
     std::string del_acl(const std::string& name);
     int sync();      // compile + upload if dirty; returns PG_* code
     void compile();  // host image only (no GPU)
-    void touch() { dirty = true, compiled = false; }
+    void touch() { dirty = true, compiled = false, port_lo_valid = false; }
+    // pg_port_intervals: the dst-port bounds of TCP and UDP over by_name, kept until the next change
+    std::vector<uint32_t> port_lo[2];
+    bool port_lo_valid = false;
     const DevTableSet* view() const;
     int iface_of(const std::string& name) const;
     std::string node_if_name() const;

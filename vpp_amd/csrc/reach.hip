@@ -13,6 +13,15 @@
 //                 -- the other order (adjacent lanes on adjacent words of one row) made every dst
 //                 load a 64-line gather and took 1.28 times as long per call. The
 //                 full words, when asked for, as 16-B vectors where a row's words are 16-B aligned
+//  k_ports_pairs  the port sweep (pg_reach_ports; ports.hpp): one lane per pair, grid-stride; the
+//                 interval loop innermost, so a pair's src and dst values are loaded once for all K
+//                 intervals. Adjacent lanes take adjacent dst of one src -- the opposite of
+//                 k_reach_pairs, because here a lane's output (row_words(K) code words, the open
+//                 count, K full words) is contiguous per pair: the dst values and the out_open
+//                 stores are coalesced, the out_codes stores too when K <= 16, and the src values
+//                 are one or two addresses per wave. The per-interval values are indexed by the
+//                 loop counter alone and arrive by scalar loads (the arrays are __restrict__
+//                 kernel arguments of their own for that). Prologues: k_reach_ends, k_reach_svcs
 //
 // No kernel takes or touches a hit counter.
 #include <hip/hip_runtime.h>
@@ -21,6 +30,7 @@
 #include <string>
 #include <vector>
 
+#include "ports.hpp"
 #include "reach.hpp"
 
 namespace pg {
@@ -222,6 +232,138 @@ int dev_reach_matrix(const DevTableSet& T, const Tuning& tu, const ReachSpecDev&
     (void)hipFree(d);
     if (rc == 0 && es != hipSuccess) {
         if (err) *err = std::string("reach matrix: ") + hipGetErrorString(es);
+        return -1;
+    }
+    return rc;
+}
+
+// ---- port sweep (ports.hpp) ----------------------------------------------------------------------
+namespace {
+
+// the hoisted end-point arrays of one form (ReachPass's first four)
+struct PortsEnds {
+    const W4* rec_s;
+    const W4* rec_d;
+    const uint32_t* cls_s;
+    const uint32_t* cls_d;
+    uint32_t n_dst;
+};
+
+// VEC: every pair's K words start 16-B aligned (K a multiple of 4, the array 16-B aligned)
+template <bool UNI, bool WIDE, bool WORDS, bool VEC>
+__global__ __launch_bounds__(kReachPairBlock) void k_ports_pairs(DevTableSet T, PortsEnds E, const W2* __restrict__ iv,
+                                                                 const uint32_t* __restrict__ len, uint32_t K,
+                                                                 uint32_t n_pairs, uint32_t* __restrict__ out_codes,
+                                                                 uint32_t* __restrict__ out_open,
+                                                                 uint32_t* __restrict__ out_words) {
+    const uint32_t rw = (uint32_t)reach_row_words(K);
+    const uint64_t step = (uint64_t)gridDim.x * kReachPairBlock;
+    // n_pairs * rw < 2^32 (the host checks), so a pair and its code words index in 32 bits
+    for (uint64_t p64 = (uint64_t)blockIdx.x * kReachPairBlock + threadIdx.x; p64 < n_pairs; p64 += step) {
+        const uint32_t p = (uint32_t)p64, i = p / E.n_dst, j = p - i * E.n_dst;
+        const uint4 sq = *reinterpret_cast<const uint4*>(E.rec_s + i);
+        const uint4 dq = *reinterpret_cast<const uint4*>(E.rec_d + j);
+        const W4 rs{sq.x, sq.y, sq.z, sq.w}, rd{dq.x, dq.y, dq.z, dq.w};
+        uint32_t* oc = out_codes + p * rw;
+        uint32_t* ow = WORDS ? out_words + (uint64_t)p * K : nullptr;
+        auto emit_code = [&](uint32_t w, uint32_t word) { oc[w] = word; };
+        auto emit_words = [&](uint32_t k0, const uint32_t(&o)[kReachQ], uint32_t valid) {
+            if constexpr (WORDS) {
+                uint32_t* q4 = ow + k0;
+                if (VEC) {  // (K a multiple of 4: every round is whole)
+                    *reinterpret_cast<uint4*>(q4) = make_uint4(o[0], o[1], o[2], o[3]);
+                } else {
+#pragma unroll
+                    for (uint32_t q = 0; q < kReachQ; q++)
+                        if (q < valid) q4[q] = o[q];
+                }
+            }
+        };
+        uint32_t open;
+        if constexpr (UNI)
+            open = ports_pair_uni<WIDE>(T, T.node, DevLoader{T.node.img}, rs, E.cls_s[i], rd, E.cls_d[j], iv, len, K,
+                                        emit_code, emit_words);
+        else
+            open = ports_pair_tab(T, rs, rd, iv, len, K, emit_code, emit_words);
+        if (out_open) out_open[p] = open;
+    }
+}
+
+template <bool UNI, bool WIDE, bool WORDS, bool VEC>
+void launch_ports(const DevTableSet& T, const PortsEnds& E, const W2* iv, const uint32_t* len, uint32_t K,
+                  uint32_t n_pairs, uint32_t* codes, uint32_t* open, uint32_t* words, uint32_t bpc, uint32_t cus,
+                  hipStream_t st) {
+    auto k = k_ports_pairs<UNI, WIDE, WORDS, VEC>;
+    hipLaunchKernelGGL(k, dim3(reach_grid(k, n_pairs, bpc, cus)), dim3(kReachPairBlock), 0, st, T, E, iv, len, K, n_pairs,
+                       codes, open, words);
+}
+template <bool UNI, bool WIDE>
+void launch_ports(const DevTableSet& T, const PortsEnds& E, const W2* iv, const uint32_t* len, uint32_t K,
+                  uint32_t n_pairs, uint32_t* codes, uint32_t* open, uint32_t* words, uint32_t bpc, uint32_t cus,
+                  hipStream_t st) {
+    const bool vec = K % 4u == 0 && ((uintptr_t)words & 15u) == 0;
+    if (!words) launch_ports<UNI, WIDE, false, false>(T, E, iv, len, K, n_pairs, codes, open, words, bpc, cus, st);
+    else if (vec) launch_ports<UNI, WIDE, true, true>(T, E, iv, len, K, n_pairs, codes, open, words, bpc, cus, st);
+    else launch_ports<UNI, WIDE, true, false>(T, E, iv, len, K, n_pairs, codes, open, words, bpc, cus, st);
+}
+
+}  // namespace
+
+int dev_reach_ports(const DevTableSet& T, const Tuning& tu, const PortsSpecDev& spec, uint32_t* out_codes,
+                    uint32_t* out_open, uint32_t* out_words, void* stream, std::string* err) {
+    const uint32_t ns = spec.n_src, nd = spec.n_dst, K = spec.K, ne = ns + nd;
+    if (!ns || !nd || !K) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    const bool form_a = reach_form_a(T.node, tu);  // (TCP / UDP: every interval takes the same form)
+    // one scratch block: [ip u32[ne] | list u32[K] | len u32[K] | cls u32[ne]] (padded to 16 B) |
+    // svc W4[K] | rec W4[ne] | g W2[K]; the host arrays go in as one copy: [ip | list | len | (cls,
+    // not copied) | svc]
+    auto pad = [](size_t b) { return (b + 15u) & ~(size_t)15u; };
+    const size_t o_ip = 0, o_list = pad(o_ip + 4u * (size_t)ne), o_len = pad(o_list + 4u * (size_t)K);
+    const size_t o_cls = pad(o_len + 4u * (size_t)K), o_svc = pad(o_cls + 4u * (size_t)ne);
+    const size_t o_rec = o_svc + 16u * (size_t)K, o_g = o_rec + 16u * (size_t)ne, total = o_g + 8u * (size_t)K;
+    std::vector<unsigned char> h(o_rec, 0);
+    std::copy(spec.src_ip, spec.src_ip + ns, reinterpret_cast<uint32_t*>(h.data() + o_ip));
+    std::copy(spec.dst_ip, spec.dst_ip + nd, reinterpret_cast<uint32_t*>(h.data() + o_ip) + ns);
+    for (uint32_t k = 0; k < K; k++) {
+        reinterpret_cast<uint32_t*>(h.data() + o_list)[k] = k;
+        reinterpret_cast<uint32_t*>(h.data() + o_len)[k] = ports_len(spec.lo, K, k);
+        reinterpret_cast<W4*>(h.data() + o_svc)[k] = reach_service((int32_t)spec.protocol, spec.src_port, spec.lo[k]);
+    }
+    unsigned char* d = nullptr;
+    REACH_CHK(hipMalloc(&d, total));
+    auto run = [&]() -> int {
+        REACH_CHK(hipMemcpy(d, h.data(), h.size(), hipMemcpyHostToDevice));
+        const uint32_t* ip = reinterpret_cast<const uint32_t*>(d + o_ip);
+        const uint32_t* dl = reinterpret_cast<const uint32_t*>(d + o_list);
+        const uint32_t* len = reinterpret_cast<const uint32_t*>(d + o_len);
+        uint32_t* cls = reinterpret_cast<uint32_t*>(d + o_cls);
+        const W4* svc = reinterpret_cast<const W4*>(d + o_svc);
+        W4* rec = reinterpret_cast<W4*>(d + o_rec);
+        W2* g = reinterpret_cast<W2*>(d + o_g);
+        const uint32_t cus = reach_cus(), bpc = tu.blocks_per_cu, np = ns * nd;
+        const unsigned ge = (ne + kReachBlock - 1) / kReachBlock, gk = (K + kReachBlock - 1) / kReachBlock;
+        if (form_a) {
+            hipLaunchKernelGGL(k_reach_ends<true>, dim3(ge), dim3(kReachBlock), 0, st, T, ip, ne, rec, cls);
+            hipLaunchKernelGGL(k_reach_svcs<true>, dim3(gk), dim3(kReachBlock), 0, st, T, svc, dl, K, g);
+            const PortsEnds E{rec, rec + ns, cls, cls + ns, nd};
+            if (T.node.wide) launch_ports<true, true>(T, E, g, len, K, np, out_codes, out_open, out_words, bpc, cus, st);
+            else launch_ports<true, false>(T, E, g, len, K, np, out_codes, out_open, out_words, bpc, cus, st);
+        } else {
+            hipLaunchKernelGGL(k_reach_ends<false>, dim3(ge), dim3(kReachBlock), 0, st, T, ip, ne, rec, nullptr);
+            hipLaunchKernelGGL(k_reach_svcs<false>, dim3(gk), dim3(kReachBlock), 0, st, T, svc, dl, K, g);
+            const PortsEnds E{rec, rec + ns, nullptr, nullptr, nd};
+            launch_ports<false, false>(T, E, g, len, K, np, out_codes, out_open, out_words, bpc, cus, st);
+        }
+        REACH_CHK(hipGetLastError());
+        return 0;
+    };
+    const int rc = run();
+    // the kernels have read the scratch block before it is released
+    const hipError_t es = hipStreamSynchronize(st);
+    (void)hipFree(d);
+    if (rc == 0 && es != hipSuccess) {
+        if (err) *err = std::string("port sweep: ") + hipGetErrorString(es);
         return -1;
     }
     return rc;

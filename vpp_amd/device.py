@@ -239,6 +239,53 @@ def unpack_reach(packed, n_svc, n_src, n_dst):
     return codes.reshape(n_svc, n_src, 16 * w.shape[2])[..., :n_dst].astype(np.uint8)
 
 
+# ---- port sweep (include/policygpu.h pg_reach_ports) ------------------------------------------
+def port_intervals(engine, protocol):
+    """the lower bounds of the elementary dst-port intervals of TCP (0) or UDP (1) over the
+    installed ACLs (pg_port_intervals): a uint32 array lo[K], lo[0] = 0, ascending; interval k ends
+    at lo[k + 1] - 1, the last at 65535"""
+    k = engine._ck(lib.pg_port_intervals(engine.h, int(protocol), None, 0))
+    lo = np.empty(k, np.uint32)
+    engine._ck(lib.pg_port_intervals(engine.h, int(protocol), lo.ctypes.data_as(C.c_void_p), k))
+    return lo
+
+
+def ports_spec(src_ips, dst_ips, protocol, src_port, n_intervals):
+    """pg_port_sweep_spec over host arrays -> (spec, the arrays it points into: keep them alive)"""
+    src = np.ascontiguousarray(src_ips, dtype=np.uint32)
+    dst = np.ascontiguousarray(dst_ips, dtype=np.uint32)
+    spec = _capi.pg_port_sweep_spec(src.ctypes.data, len(src), dst.ctypes.data, len(dst), int(protocol),
+                                    int(src_port), 0, int(n_intervals))
+    return spec, (src, dst)
+
+
+def reach_ports(engine, src_ips, dst_ips, protocol, src_port=40000, open_count=False, words=False, stream=None):
+    """testConnection of every (src, dst) on every dst port of TCP / UDP on the GPU (pg_reach_ports),
+    one evaluation per elementary port interval -> (lo, codes[, open][, words]): the interval bounds
+    (port_intervals), the packed ConnActions as an int32 tensor [n_src, n_dst, row_words(K)] (2 bits
+    per interval, unpack_ports), with ``open_count`` the open (ALLOW) ports per pair, int32 [n_src,
+    n_dst], and with ``words`` the full verdict words, int32 [n_src, n_dst, K]. The call never
+    touches the hit counters."""
+    lo = port_intervals(engine, protocol)
+    k = len(lo)
+    spec, keep = ports_spec(src_ips, dst_ips, protocol, src_port, k)
+    n_src, n_dst = spec.n_src, spec.n_dst
+    codes = torch.empty((n_src, n_dst, reach_row_words(k)), dtype=torch.int32, device="cuda")
+    n_open = torch.empty((n_src, n_dst), dtype=torch.int32, device="cuda") if open_count else None
+    full = torch.empty((n_src, n_dst, k), dtype=torch.int32, device="cuda") if words else None
+    if codes.numel():  # (an empty tensor has no address to hand over; the call would write nothing)
+        engine._ck(lib.pg_reach_ports(engine.h, C.byref(spec), codes.data_ptr(),
+                                      n_open.data_ptr() if open_count else None,
+                                      full.data_ptr() if words else None, _stream_ptr(stream)))
+    del keep
+    return (lo, codes) + ((n_open,) if open_count else ()) + ((full,) if words else ())
+
+
+def unpack_ports(codes, n_src, n_dst, k):
+    """packed sweep codes (tensor or array) -> uint8 ConnActions [n_src, n_dst, K]"""
+    return unpack_reach(codes, n_src, n_dst, k)
+
+
 def unpack(out_u32):
     w = out_u32.astype(np.uint32)
     return (w >> 30).astype(np.int64), (w & 0x3FFFFFFF).astype(np.int64)

@@ -348,6 +348,54 @@ class Engine:
             torch.cuda.synchronize()
         return D.unpack_reach(packed, len(services), len(src), len(dst))
 
+    def port_intervals(self, protocol):
+        """lower bounds lo[K] (uint32, lo[0] = 0, ascending) of the elementary dst-port intervals of
+        TCP (0) or UDP (1) over the installed ACLs (pg_port_intervals): inside one interval every
+        pair has one verdict"""
+        from . import device as D
+        return D.port_intervals(self, protocol)
+
+    def debug_reach_ports_host(self, src_ips, dst_ips, protocol, src_port=40000, node=True, n_intervals=None):
+        """TESTS ONLY: pg_reach_ports's code run on the host (pg_debug_reach_ports_host).
+        -> (lo u32[K], codes u32 [n_src, n_dst, row_words(K)], open u32 [n_src, n_dst], words u32
+        [n_src, n_dst, K]); the outputs are pre-filled with 0xFFFFFFFF."""
+        import numpy as np
+        from . import device as D
+        lo = self.port_intervals(protocol)
+        k = len(lo) if n_intervals is None else n_intervals
+        spec, keep = D.ports_spec(src_ips, dst_ips, protocol, src_port, k)
+        codes = np.full((spec.n_src, spec.n_dst, lib.pg_reach_row_words(k)), 0xFFFFFFFF, np.uint32)
+        n_open = np.full((spec.n_src, spec.n_dst), 0xFFFFFFFF, np.uint32)
+        full = np.full((spec.n_src, spec.n_dst, k), 0xFFFFFFFF, np.uint32)
+        p = lambda x: x.ctypes.data_as(C.c_void_p)
+        self._ck(lib.pg_debug_reach_ports_host(self.h, C.byref(spec), p(codes), p(n_open), p(full), int(node)))
+        del keep
+        return lo, codes, n_open, full
+
+    def open_ports(self, src_pods, dst_pods, protocol, src_port=40000, host=False):
+        """Between these pods, which dst ports are open? One pg_reach_ports call over all 65,536 dst
+        ports of TCP (0) or UDP (1). -> (ranges, open): ranges[i][j] the maximal (lo, hi) port
+        ranges, ascending, on which src pod i reaches dst pod j (ConnAction ALLOW; adjacent ALLOW
+        intervals merged), open a uint32 array [n_src, n_dst] of how many ports that is. Pods as in
+        reachability. ``host``: TESTS ONLY, the host twin instead of the GPU."""
+        import numpy as np
+        from . import device as D
+        src, dst = self._pod_ips(src_pods), self._pod_ips(dst_pods)
+        if host:
+            lo, codes, n_open, _ = self.debug_reach_ports_host(src, dst, protocol, src_port)
+        else:
+            import torch
+            lo, codes, n_open = D.reach_ports(self, src, dst, protocol, src_port, open_count=True)
+            torch.cuda.synchronize()
+            n_open = n_open.cpu().numpy().view(np.uint32)
+        allow = D.unpack_ports(codes, len(src), len(dst), len(lo)) == 2   # PG_CONN_ALLOW
+        # a range starts where ALLOW begins and ends where it stops: the edges of the 0-padded row
+        edge = np.diff(np.pad(allow.astype(np.int8), ((0, 0), (0, 0), (1, 1))), axis=2)
+        hi = np.append(lo[1:], 65536).astype(np.int64) - 1
+        ranges = [[list(zip(lo[edge[i, j, :-1] == 1].tolist(), hi[edge[i, j, 1:] == -1].tolist()))
+                   for j in range(len(dst))] for i in range(len(src))]
+        return ranges, n_open
+
     def debug_walk_stats(self, table_id, src, dst, dport, proto):
         """MEASUREMENT: per tuple, the loads a SINGLE launch on table_id makes of the table's
         structure (pg_debug_walk_stats) -> (lds_reads u32[n], mem_reads u32[n], launch STAGE)"""
