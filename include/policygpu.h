@@ -542,6 +542,63 @@ int pg_reach_ports(pg_ctx* ctx, const pg_port_sweep_spec* spec, uint32_t* out_co
 int pg_debug_reach_ports_host(pg_ctx* ctx, const pg_port_sweep_spec* spec, uint32_t* out_codes, uint32_t* out_open,
                               uint32_t* out_words, int flags);
 
+/* ---- reachability diff: the cells two audit results differ in, on the device --------------
+ * "What did this policy change open or close?" pg_reach_matrix (out_packed) and pg_reach_ports
+ * (out_codes) write one layout: 2 bits per cell, 16 cells per word, rows of row_words =
+ * pg_reach_row_words(n_cols) words, padding zero -- a matrix has n_svc * n_src rows of n_dst
+ * cells, a sweep n_src * n_dst rows of K cells. pg_reach_diff compares two such results of one
+ * shape on the device, so neither is copied to the host: typically the live engine's and that of
+ * a staging engine with the candidate policy (the two inputs may come from different contexts on
+ * the same device; ctx only names the device and its launch knobs).
+ *   A cell is selected when its two ConnActions differ and bit (4 * before + after) of
+ *   spec->transitions is set; the four diagonal bits are ignored. PG_DIFF_OPENED selects what
+ *   became ALLOW, PG_DIFF_CLOSED what stopped being ALLOW.
+ *   *n_changes   host, required: the number of selected cells; it may exceed spec->cap
+ *   changes      device, optional, spec->cap entries: the first min(*n_changes, cap) selected
+ *                cells in ascending (row, column) order; entries past that are not written. Null,
+ *                or cap == 0: count only
+ *   row_changes  device, optional, n_rows words: the selected cells of every row (every row is
+ *                written)
+ *   trans        host, optional: trans[4 * b + a] = the cells with ConnAction b before and a
+ *                after, over ALL cells whatever `transitions` selects, the diagonal included: the
+ *                16 values sum to n_rows * n_cols
+ * The padding bits of a row's last word are never compared (they are masked, not trusted). Two
+ * port sweeps are comparable only over the same partition lo[] (pg_port_intervals equal on both
+ * engines); the call cannot check that. The call reads no table and triggers no compile, and it
+ * never touches the hit counters or their snapshots. It enqueues on hip_stream and synchronises
+ * that stream before it returns, because the count comes back to the host. n_rows == 0: PG_OK,
+ * *n_changes = 0, trans zeroed, nothing else written. PG_EINVAL: a null spec, before, after or
+ * n_changes; n_cols 0 or above 2^20; n_rows >= 2^32; n_rows * row_words >= 2^32. */
+#define PG_DIFF_ALL    0xFFFFu
+#define PG_DIFF_OPENED 0x4044u   /* before != ALLOW, after == ALLOW: bits 2, 6, 14 */
+#define PG_DIFF_CLOSED 0x0B00u   /* before == ALLOW, after != ALLOW: bits 8, 9, 11 */
+typedef struct pg_reach_change {
+    uint32_t row;    /* (v * n_src + i) of a matrix, (i * n_dst + j) of a port sweep */
+    uint32_t cell;   /* bits 19-0 column (dst j / interval k), 29-28 ConnAction before, 31-30 after */
+} pg_reach_change;
+typedef struct pg_reach_diff_spec {
+    const uint32_t* before;  /* device, n_rows * pg_reach_row_words(n_cols) words */
+    const uint32_t* after;   /* device, same shape */
+    uint64_t n_rows;
+    uint32_t n_cols;         /* 1 .. 2^20 */
+    uint32_t transitions;    /* bit (4 * before + after) set: that transition is selected */
+    uint64_t cap;            /* entries `changes` can hold */
+} pg_reach_diff_spec;
+int pg_reach_diff(pg_ctx* ctx, const pg_reach_diff_spec* spec, pg_reach_change* changes, uint32_t* row_changes,
+                  uint64_t* n_changes, uint64_t trans[16], void* hip_stream);
+/* TESTS ONLY -- never on the audit path: pg_reach_diff's per-word code (diff.hpp, the functions the
+ * kernels call) on the host; before, after, changes and row_changes are host arrays. Does not touch
+ * the device. */
+int pg_debug_reach_diff_host(pg_ctx* ctx, const pg_reach_diff_spec* spec, pg_reach_change* changes,
+                             uint32_t* row_changes, uint64_t* n_changes, uint64_t trans[16]);
+/* TESTS ONLY: how a pg_reach_diff over n_words = n_rows * row_words words is cut under this context's
+ * knobs (blocks_per_cu), from the one function the launch itself uses (diff.hpp diff_plan): the tile
+ * (words a workgroup takes per step), the workgroups, and the words of the contiguous chunk each one
+ * owns (a multiple of the tile). Queries the device's size and the kernels' occupancy; launches
+ * nothing. */
+int pg_debug_reach_diff_plan(pg_ctx* ctx, uint64_t n_words, uint32_t* tile_words, uint32_t* grid,
+                             uint64_t* chunk_words);
+
 /* ---- policy configurator ------------------------------------------
  * configurator.PolicyConfiguratorAPI / Txn (plugins/policy/configurator/configurator_api.go:28-54,
  * configurator_impl.go:104-472): K8s-shaped policies per pod -> ordered ContivRule lists

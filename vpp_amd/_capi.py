@@ -20,6 +20,8 @@ LIB_PATH = os.path.join(_HERE, "libpolicygpu.so")
 
 PG_OK, PG_ENOENT, PG_EIO, PG_ENOMEM, PG_EINVAL, PG_EFAULT = 0, -2, -5, -12, -22, -14
 MODE_SINGLE, MODE_PERPOD, MODE_CONN = 0, 1, 2
+# pg_reach_diff transitions: bit 4 * before + after (ConnActions; ALLOW = 2)
+DIFF_ALL, DIFF_OPENED, DIFF_CLOSED = 0xFFFF, 0x4044, 0x0B00
 ORIENT_INGRESS, ORIENT_EGRESS = 0, 1
 
 
@@ -94,6 +96,11 @@ class pg_reach_spec(C.Structure):
 class pg_port_sweep_spec(C.Structure):
     _fields_ = [("src_ip", C.c_void_p), ("n_src", C.c_size_t), ("dst_ip", C.c_void_p), ("n_dst", C.c_size_t),
                 ("protocol", C.c_int32), ("src_port", C.c_uint16), ("_pad", C.c_uint16), ("n_intervals", C.c_size_t)]
+
+
+class pg_reach_diff_spec(C.Structure):
+    _fields_ = [("before", C.c_void_p), ("after", C.c_void_p), ("n_rows", C.c_uint64), ("n_cols", C.c_uint32),
+                ("transitions", C.c_uint32), ("cap", C.c_uint64)]
 
 
 class pg_pod_id(C.Structure):
@@ -243,6 +250,10 @@ _SIGS = {
     "pg_port_intervals": (C.c_int, [_P, C.c_int, _P, C.c_size_t]),
     "pg_reach_ports": (C.c_int, [_P, C.POINTER(pg_port_sweep_spec), _P, _P, _P, _P]),
     "pg_debug_reach_ports_host": (C.c_int, [_P, C.POINTER(pg_port_sweep_spec), _P, _P, _P, C.c_int]),
+    "pg_reach_diff": (C.c_int, [_P, C.POINTER(pg_reach_diff_spec), _P, _P, C.POINTER(C.c_uint64), _P, _P]),
+    "pg_debug_reach_diff_host": (C.c_int, [_P, C.POINTER(pg_reach_diff_spec), _P, _P, C.POINTER(C.c_uint64), _P]),
+    "pg_debug_reach_diff_plan": (C.c_int, [_P, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                           C.POINTER(C.c_uint64)]),
     "pg_session_rules_new": (_P, [C.c_char_p]),
     "pg_session_rules_free": (None, [_P]),
     "pg_session_rules_clear": (C.c_int, [_P]),

@@ -8,6 +8,7 @@
 
 #include "capi_internal.hpp"
 #include "classify.hpp"
+#include "diff.hpp"
 #include "ports.hpp"
 #include "reach.hpp"
 
@@ -1587,6 +1588,92 @@ int pg_debug_reach_ports_host(pg_ctx* ctx, const pg_port_sweep_spec* spec, uint3
     if (!form_a) host_ports_pairs<false, false>(T, P);
     else if (T.node.wide) host_ports_pairs<true, true>(T, P);
     else host_ports_pairs<true, false>(T, P);
+    return PG_OK;
+    GUARD_END(ctx)
+}
+
+}  // extern "C"
+
+// ---- reachability diff (diff.hpp) ----------------------------------------------------------------
+namespace {
+static_assert(sizeof(pg_reach_change) == sizeof(DiffEntry), "pg_reach_change is diff.hpp's DiffEntry");
+
+// argument checks shared by pg_reach_diff and its host twin: PG_OK with *empty set when there is no
+// row (then *n_changes and trans are zeroed here)
+int diff_args(pg_ctx* ctx, const pg_reach_diff_spec* spec, uint64_t* n_changes, uint64_t* trans, bool* empty) {
+    if (!ctx) return PG_EINVAL;
+    if (!spec || !spec->before || !spec->after || !n_changes)
+        return fail(ctx, PG_EINVAL, "null spec, before, after or n_changes");
+    if (!spec->n_cols || spec->n_cols > kDiffMaxCols) return fail(ctx, PG_EINVAL, "n_cols is 0 or above 2^20");
+    if (spec->n_rows >> 32) return fail(ctx, PG_EINVAL, "n_rows reaches 2^32");
+    // (n_rows < 2^32 and row_words <= 2^16: the product fits 64 bits)
+    if (spec->n_rows * reach_row_words(spec->n_cols) >> 32) return fail(ctx, PG_EINVAL, "n_rows * row_words reaches 2^32");
+    *empty = !spec->n_rows;
+    if (*empty) {
+        *n_changes = 0;
+        if (trans) std::fill(trans, trans + 16, (uint64_t)0);
+    }
+    return PG_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int pg_reach_diff(pg_ctx* ctx, const pg_reach_diff_spec* spec, pg_reach_change* changes, uint32_t* row_changes,
+                  uint64_t* n_changes, uint64_t* trans, void* stream) {
+    GUARD_BEGIN
+    bool empty = false;
+    if (int rc = diff_args(ctx, spec, n_changes, trans, &empty)) return rc;
+    if (empty) return PG_OK;
+    DEVICE_GUARD(ctx);
+    const DiffSpecDev sd{spec->before, spec->after, (uint32_t)spec->n_rows, spec->n_cols, spec->transitions, spec->cap};
+    std::string err;
+    if (dev_reach_diff(ctx->eng.tune.blocks_per_cu, sd, reinterpret_cast<DiffEntry*>(changes), row_changes, n_changes, trans,
+                       stream, &err) != 0)
+        return fail(ctx, PG_EIO, err);
+    return PG_OK;
+    GUARD_END(ctx)
+}
+
+int pg_debug_reach_diff_host(pg_ctx* ctx, const pg_reach_diff_spec* spec, pg_reach_change* changes,
+                             uint32_t* row_changes, uint64_t* n_changes, uint64_t* trans) {
+    GUARD_BEGIN
+    bool empty = false;
+    if (int rc = diff_args(ctx, spec, n_changes, trans, &empty)) return rc;
+    if (empty) return PG_OK;
+    const uint32_t rw = (uint32_t)reach_row_words(spec->n_cols), n_rows = (uint32_t)spec->n_rows;
+    const uint64_t cap = changes ? spec->cap : 0;
+    uint64_t n = 0, hist[16] = {0};
+    // every word in order, as the kernels' lanes run it
+    for (uint32_t row = 0; row < n_rows; row++) {
+        uint32_t in_row = 0;
+        for (uint32_t jw = 0; jw < rw; jw++) {
+            const uint32_t b = spec->before[(uint64_t)row * rw + jw], a = spec->after[(uint64_t)row * rw + jw];
+            const uint32_t valid = diff_valid(spec->n_cols, jw);
+            const DiffEq eb = diff_eq(b), ea = diff_eq(a);
+            uint32_t h[16] = {0};
+            if (b == a) diff_hist_same(eb, valid, h);
+            else diff_hist(eb, ea, valid, h);
+            for (int k = 0; k < 16; k++) hist[k] += h[k];
+            for (uint32_t m = diff_selected(eb, ea, b ^ a, valid, spec->transitions); m; m &= m - 1u) {
+                if (n < cap) changes[n] = pg_reach_change{row, diff_cell(jw, (uint32_t)__builtin_ctz(m), b, a)};
+                n++, in_row++;
+            }
+        }
+        if (row_changes) row_changes[row] = in_row;
+    }
+    *n_changes = n;
+    if (trans) std::copy(hist, hist + 16, trans);
+    return PG_OK;
+    GUARD_END(ctx)
+}
+
+int pg_debug_reach_diff_plan(pg_ctx* ctx, uint64_t n_words, uint32_t* tile_words, uint32_t* grid, uint64_t* chunk_words) {
+    if (!ctx || !tile_words || !grid || !chunk_words) return PG_EINVAL;
+    GUARD_BEGIN
+    DEVICE_GUARD(ctx);
+    const DiffPlan p = dev_diff_plan(n_words, ctx->eng.tune.blocks_per_cu);
+    *tile_words = p.tile_words, *grid = p.grid, *chunk_words = p.chunk_words;
     return PG_OK;
     GUARD_END(ctx)
 }

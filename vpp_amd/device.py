@@ -286,6 +286,55 @@ def unpack_ports(codes, n_src, n_dst, k):
     return unpack_reach(codes, n_src, n_dst, k)
 
 
+# ---- reachability diff (include/policygpu.h pg_reach_diff) -----------------------------------
+DIFF_ALL, DIFF_OPENED, DIFF_CLOSED = _capi.DIFF_ALL, _capi.DIFF_OPENED, _capi.DIFF_CLOSED
+
+
+def reach_diff(engine, before, after, n_cols, transitions=DIFF_ALL, cap=None, row_changes=False, stream=None):
+    """The cells in which two packed audit results differ, on the GPU (pg_reach_diff). ``before`` and
+    ``after`` are int32 device tensors of one shape [..., row_words(n_cols)]: two reach_matrix results
+    (n_cols = n_dst) or two reach_ports code tensors over one partition (n_cols = K); rows are the
+    leading dimensions flattened. -> (n_changes, changes, trans, row_changes): the number of selected
+    cells, the first min(n_changes, cap) of them in (row, column) order as an int32 tensor [m, 2]
+    (unpack_changes), the uint64 array trans[before, after] over all cells, and with ``row_changes``
+    an int32 tensor [n_rows], else None. ``cap`` None: a count-only call first, then one sized
+    exactly; 0: count only. The call never touches the hit counters."""
+    rw = reach_row_words(n_cols)
+    if before.shape != after.shape or before.dtype != torch.int32 or after.dtype != torch.int32:
+        raise ValueError("before and after must be int32 tensors of one shape")
+    if not (before.is_contiguous() and after.is_contiguous()) or (before.numel() and before.shape[-1] != rw):
+        raise ValueError("contiguous tensors [..., row_words(n_cols)] expected")
+    n_rows = before.numel() // rw
+    rows = torch.empty(n_rows, dtype=torch.int32, device="cuda") if row_changes else None
+    trans = np.zeros(16, np.uint64)
+    if n_rows == 0:  # (an empty tensor has no address to hand over; the call would write nothing)
+        return 0, torch.empty((0, 2), dtype=torch.int32, device="cuda"), trans.reshape(4, 4), rows
+
+    def call(changes, cap, rows, want_trans):
+        spec = _capi.pg_reach_diff_spec(before.data_ptr(), after.data_ptr(), n_rows, int(n_cols), int(transitions), cap)
+        n = C.c_uint64()
+        engine._ck(lib.pg_reach_diff(engine.h, C.byref(spec), changes.data_ptr() if cap else None,
+                                     rows.data_ptr() if rows is not None else None, C.byref(n),
+                                     trans.ctypes.data_as(C.c_void_p) if want_trans else None, _stream_ptr(stream)))
+        return n.value
+
+    if cap is None:
+        cap = call(None, 0, None, False)
+    changes = torch.empty((cap, 2), dtype=torch.int32, device="cuda")
+    n = call(changes, cap, rows, True)
+    return n, changes[:min(n, cap)], trans.reshape(4, 4), rows
+
+
+def unpack_changes(changes):
+    """pg_reach_change entries (tensor or array [m, 2]) -> (row, column, ConnAction before, after)
+    arrays"""
+    if isinstance(changes, torch.Tensor):
+        changes = changes.cpu().numpy()
+    c = np.ascontiguousarray(changes).view(np.uint32).reshape(-1, 2)
+    cell = c[:, 1]
+    return c[:, 0].copy(), cell & 0xFFFFF, ((cell >> 28) & 3).astype(np.uint8), (cell >> 30).astype(np.uint8)
+
+
 def unpack(out_u32):
     w = out_u32.astype(np.uint32)
     return (w >> 30).astype(np.int64), (w & 0x3FFFFFFF).astype(np.int64)

@@ -396,6 +396,58 @@ class Engine:
                    for j in range(len(dst))] for i in range(len(src))]
         return ranges, n_open
 
+    def debug_reach_diff_host(self, before, after, n_cols, transitions=_capi.DIFF_ALL, cap=None, row_changes=True):
+        """TESTS ONLY: pg_reach_diff's per-word code run on the host (pg_debug_reach_diff_host) over
+        numpy arrays of packed words [..., row_words(n_cols)]. ``cap`` None: as many entries as there
+        are cells. -> (n_changes, changes u32 [cap, 2], trans u64 [4, 4], row_changes u32 [n_rows] or
+        None); changes and row_changes are pre-filled with 0xFFFFFFFF."""
+        import numpy as np
+        b = np.ascontiguousarray(before, dtype=np.uint32)
+        a = np.ascontiguousarray(after, dtype=np.uint32)
+        rw = lib.pg_reach_row_words(n_cols)
+        n_rows = b.size // rw
+        cap = n_rows * int(n_cols) if cap is None else cap
+        changes = np.full((cap, 2), 0xFFFFFFFF, np.uint32)
+        rows = np.full(n_rows, 0xFFFFFFFF, np.uint32) if row_changes else None
+        trans = np.full(16, 0xFFFFFFFFFFFFFFFF, np.uint64)
+        p = lambda x: x.ctypes.data_as(C.c_void_p)
+        spec = _capi.pg_reach_diff_spec(b.ctypes.data, a.ctypes.data, n_rows, int(n_cols), int(transitions), cap)
+        n = C.c_uint64()
+        self._ck(lib.pg_debug_reach_diff_host(self.h, C.byref(spec), p(changes) if cap else None,
+                                              p(rows) if row_changes else None, C.byref(n), p(trans)))
+        return n.value, changes, trans.reshape(4, 4), rows
+
+    def debug_reach_diff_plan(self, n_words):
+        """TESTS ONLY: how pg_reach_diff cuts n_words words under this context's knobs
+        (pg_debug_reach_diff_plan) -> {tile_words, grid, chunk_words}"""
+        t, g, c = C.c_uint32(), C.c_uint32(), C.c_uint64()
+        self._ck(lib.pg_debug_reach_diff_plan(self.h, int(n_words), C.byref(t), C.byref(g), C.byref(c)))
+        return {"tile_words": t.value, "grid": g.value, "chunk_words": c.value}
+
+    def reachability_diff(self, baseline, src_pods, dst_pods, services, transitions=_capi.DIFF_ALL, host=False):
+        """What a policy change opened or closed: the (service, src pod, dst pod) whose ConnAction
+        under this engine differs from that under ``baseline`` (another Engine on the same device),
+        by two pg_reach_matrix calls and one pg_reach_diff. -> ([(service index, src pod, dst pod,
+        ConnAction before, after), ...] in (service, src, dst) order with the pods as given,
+        trans): ``transitions`` selects what is listed (DIFF_OPENED, DIFF_CLOSED, ...), trans is the
+        uint64 array [before, after] over all pairs. ``host``: TESTS ONLY, the host twins."""
+        from . import device as D
+        src, dst = self._pod_ips(src_pods), self._pod_ips(dst_pods)
+        if host:
+            b = baseline.debug_reach_matrix_host(src, dst, services, words=False)
+            a = self.debug_reach_matrix_host(src, dst, services, words=False)
+            n, changes, trans, _ = self.debug_reach_diff_host(b, a, len(dst), transitions, row_changes=False)
+            changes = changes[:n]
+        else:
+            b = D.reach_matrix(baseline, src, dst, services)
+            a = D.reach_matrix(self, src, dst, services)
+            n, changes, trans, _ = D.reach_diff(self, b, a, len(dst), transitions)
+        row, col, cb, ca = D.unpack_changes(changes)
+        ns = max(1, len(src))
+        out = [(int(r) // ns, src_pods[int(r) % ns], dst_pods[int(j)], int(x), int(y))
+               for r, j, x, y in zip(row, col, cb, ca)]
+        return out, trans
+
     def debug_walk_stats(self, table_id, src, dst, dport, proto):
         """MEASUREMENT: per tuple, the loads a SINGLE launch on table_id makes of the table's
         structure (pg_debug_walk_stats) -> (lds_reads u32[n], mem_reads u32[n], launch STAGE)"""
