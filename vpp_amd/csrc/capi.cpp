@@ -8,9 +8,6 @@
 
 #include "capi_internal.hpp"
 #include "classify.hpp"
-#include "diff.hpp"
-#include "ports.hpp"
-#include "reach.hpp"
 
 using namespace pg;
 
@@ -91,30 +88,6 @@ ACLPtr to_acl(const pg_acl& a) {
     return acl;
 }
 
-int fail(pg_ctx* c, int code, const std::string& msg) {
-    if (c) c->eng.last_error = msg;
-    return code;
-}
-
-// Every entry point that touches the device makes the context's GPU current for the call and
-// restores the caller's afterwards: contexts on different GPUs can share a process, and a cgo
-// caller's goroutine may move between OS threads between two calls.
-struct DeviceGuard {
-    int prev = -1, dev = 0;
-    bool ok = true;
-    std::string err;
-    explicit DeviceGuard(const pg_ctx* c) : dev(c->eng.device) {
-        if (dev_get_device(&prev) != 0) prev = -1;
-        if (prev != dev) ok = dev_set_device(dev, &err) == 0;
-    }
-    ~DeviceGuard() {
-        if (prev >= 0 && prev != dev) (void)dev_set_device(prev, nullptr);
-    }
-};
-#define DEVICE_GUARD(ctx)                                             \
-    DeviceGuard guard_(ctx);                                          \
-    if (!guard_.ok) return fail(ctx, PG_EIO, "set device: " + guard_.err)
-
 std::string json_escape(const std::string& s) {
     std::string o;
     for (char ch : s) {
@@ -134,16 +107,6 @@ uint32_t pkt_key_host(int proto, uint16_t port) {
 }
 
 }  // namespace
-
-#define GUARD_BEGIN try {
-#define GUARD_END(ctx)                                         \
-    }                                                          \
-    catch (const std::exception& e) {                          \
-        return fail(ctx, PG_EFAULT, e.what());                 \
-    }                                                          \
-    catch (...) {                                              \
-        return fail(ctx, PG_EFAULT, "unknown C++ exception");  \
-    }
 
 extern "C" {
 
@@ -650,9 +613,7 @@ int pg_debug_node_launch_plan(pg_ctx* ctx, int mode, int counters, pg_node_launc
 }
 }  // extern "C"
 
-namespace {
-// host view of the compiled table set (pointers into the host image)
-DevTableSet host_view(const HostTableSet& h) {
+DevTableSet pg::host_view(const HostTableSet& h) {
     DevTableSet v{};
     v.rules = h.rules.data();
     v.tabs = h.tabs.data();
@@ -679,6 +640,7 @@ DevTableSet host_view(const HostTableSet& h) {
     return v;
 }
 
+namespace {
 template <int MODE, int Q, bool PRED, bool CM, bool UNI, bool WIDE>
 void host_q(const DevTableSet& T, bool node, int table_id, const pg_tuple_soa* t, uint64_t i, uint32_t* out,
             const Hist& h) {
@@ -1326,354 +1288,6 @@ int pg_connections(pg_ctx* ctx, const pg_conn_query* q, size_t n, int32_t* out, 
         out[i] = (int32_t)(w >> 30);
         if (out_slot) out_slot[i] = w & 0x3FFFFFFFu;
     }
-    return PG_OK;
-    GUARD_END(ctx)
-}
-
-}  // extern "C"
-
-// ---- reachability matrix (reach.hpp) -------------------------------------------------------------
-namespace {
-// argument checks shared by pg_reach_matrix and its host twin: PG_OK with *empty set when there
-// is nothing to do
-int reach_args(pg_ctx* ctx, const pg_reach_spec* spec, const uint32_t* out_packed, bool* empty) {
-    if (!ctx || !spec || !out_packed) return PG_EINVAL;
-    if (spec->n_src > kReachMaxSide || spec->n_dst > kReachMaxSide) return fail(ctx, PG_EINVAL, "a side longer than 2^20");
-    if (spec->n_svc > kReachMaxSvc) return fail(ctx, PG_EINVAL, "more than 4096 services");
-    *empty = !spec->n_src || !spec->n_dst || !spec->n_svc;
-    if (!*empty && (!spec->src_ip || !spec->dst_ip || !spec->services)) return fail(ctx, PG_EINVAL, "null spec array");
-    return PG_OK;
-}
-std::vector<W4> reach_services(const pg_reach_spec* spec) {
-    std::vector<W4> v(spec->n_svc);
-    for (size_t k = 0; k < spec->n_svc; k++)
-        v[k] = reach_service(spec->services[k].protocol, spec->services[k].src_port, spec->services[k].dst_port);
-    return v;
-}
-
-// every word of the services `list` (one form's), as k_reach_pairs runs them
-template <bool UNI, bool WIDE>
-void host_reach_pairs(const DevTableSet& T, const ReachPass& P) {
-    const uint64_t rw = reach_row_words(P.n_dst);
-    const DevLoader img{T.node.img};
-    for (uint32_t k = 0; k < P.n_list; k++) {
-        const uint32_t v = P.svc_list[k];
-        for (uint32_t i = 0; i < P.n_src; i++) {
-            const uint64_t row = (uint64_t)v * P.n_src + i;
-            for (uint64_t jw = 0; jw < rw; jw++) {
-                const uint32_t j0 = (uint32_t)jw * kReachWordPairs;
-                uint32_t* ow = P.out_words ? P.out_words + row * P.n_dst + j0 : nullptr;
-                auto emit = [&](uint32_t r, const uint32_t(&o)[kReachQ], uint32_t valid) {
-                    for (uint32_t q = 0; ow && q < valid; q++) ow[r * kReachQ + q] = o[q];
-                };
-                uint32_t packed;
-                if constexpr (UNI)
-                    packed = reach_word_uni<WIDE>(T, T.node, img, P.rec_s[i], P.cls_s[i], P.rec_d, P.cls_d, j0, P.n_dst,
-                                                  P.svc[v], emit);
-                else
-                    packed = reach_word_tab(T, P.rec_s[i], P.rec_d, j0, P.n_dst, P.svc[v], emit);
-                P.out_packed[row * rw + jw] = packed;
-            }
-        }
-    }
-}
-}  // namespace
-
-extern "C" {
-
-size_t pg_reach_row_words(size_t n_dst) { return (size_t)reach_row_words(n_dst); }
-
-int pg_reach_matrix(pg_ctx* ctx, const pg_reach_spec* spec, uint32_t* out_packed, uint32_t* out_words,
-                    void* stream) {
-    bool empty = false;
-    if (int rc = reach_args(ctx, spec, out_packed, &empty)) return rc;
-    if (empty) return PG_OK;
-    DEVICE_GUARD(ctx);
-    GUARD_BEGIN
-    int rc = ctx->eng.sync();
-    if (rc) return rc;
-    const DevTableSet& T = *ctx->eng.view();
-    const std::vector<W4> svc = reach_services(spec);
-    const ReachSpecDev sd{spec->src_ip, spec->dst_ip, svc.data(), (uint32_t)spec->n_src, (uint32_t)spec->n_dst,
-                          (uint32_t)spec->n_svc};
-    std::string err;
-    if (dev_reach_matrix(T, ctx->eng.tune, sd, out_packed, out_words, stream, &err) != 0 ||
-        dev_mark_use(ctx->eng.cur, stream, false, &err) != 0)
-        return fail(ctx, PG_EIO, err);
-    return PG_OK;
-    GUARD_END(ctx)
-}
-
-int pg_debug_reach_matrix_host(pg_ctx* ctx, const pg_reach_spec* spec, uint32_t* out_packed, uint32_t* out_words,
-                               int flags) {
-    bool empty = false;
-    if (int rc = reach_args(ctx, spec, out_packed, &empty)) return rc;
-    GUARD_BEGIN
-    if (empty) return PG_OK;
-    Engine& E = ctx->eng;
-    if (!E.compiled) E.compile();
-    const DevTableSet T = host_view(E.host);
-    const uint32_t ns = (uint32_t)spec->n_src, nd = (uint32_t)spec->n_dst, nv = (uint32_t)spec->n_svc, ne = ns + nd;
-    const std::vector<W4> svc = reach_services(spec);
-    const bool form_a = (flags & 1) && reach_form_a(T.node, E.tune);
-    std::vector<uint32_t> la, lb;  // the services of each form
-    for (uint32_t v = 0; v < nv; v++) (form_a && svc[v].x <= 2u ? la : lb).push_back(v);
-    auto ip_of = [&](uint32_t e) { return e < ns ? spec->src_ip[e] : spec->dst_ip[e - ns]; };
-    std::vector<W4> rec(ne);
-    std::vector<uint32_t> cls(ne);
-    std::vector<W2> g(nv);
-    if (!la.empty()) {
-        const DevLoader img{T.node.img};
-        for (uint32_t e = 0; e < ne; e++) reach_end_uni(T.node, img, ip_of(e), &rec[e], &cls[e]);
-        for (uint32_t v : la) g[v] = reach_svc_uni(T.node, img, svc[v]);
-        const ReachPass P{rec.data(), rec.data() + ns, cls.data(), cls.data() + ns, g.data(), la.data(),
-                          (uint32_t)la.size(), ns, nd, out_packed, out_words};
-        if (T.node.wide) host_reach_pairs<true, true>(T, P);
-        else host_reach_pairs<true, false>(T, P);
-    }
-    if (!lb.empty()) {
-        for (uint32_t e = 0; e < ne; e++) rec[e] = reach_end_tab(T, ip_of(e));
-        for (uint32_t v : lb) g[v] = reach_svc_tab(svc[v]);
-        const ReachPass P{rec.data(), rec.data() + ns, nullptr, nullptr, g.data(), lb.data(), (uint32_t)lb.size(), ns, nd,
-                          out_packed, out_words};
-        host_reach_pairs<false, false>(T, P);
-    }
-    return PG_OK;
-    GUARD_END(ctx)
-}
-
-}  // extern "C"
-
-// ---- port sweep (ports.hpp) ----------------------------------------------------------------------
-namespace {
-// The elementary dst-port intervals of a protocol: 0 and, of every installed rule whose L4 section
-// of that protocol carries a dst range, the two bounds as evalACL compares them (after its uint16
-// truncation, aclengine_mock.go:589): lower & 0xFFFF and (upper & 0xFFFF) + 1. Rules that never
-// reach the comparison (a structural FAILURE before it, an empty range) only add cuts. Both
-// protocols' bounds are kept with the engine until the next ACL change (Engine::touch).
-const std::vector<uint32_t>& port_bounds(Engine& E, int protocol) {
-    if (!E.port_lo_valid) {
-        for (int p : {PG_PROTO_TCP, PG_PROTO_UDP}) {
-            std::vector<uint32_t>& lo = E.port_lo[p];
-            lo.assign(1, 0u);
-            for (const auto& kv : E.by_name)
-                for (const AclRule& r : kv.second->rules) {
-                    const L4Section& s = p == PG_PROTO_TCP ? r.tcp : r.udp;
-                    if (!s.present || !s.has_dst) continue;
-                    lo.push_back(s.dst.lower & 0xFFFFu);
-                    lo.push_back((s.dst.upper & 0xFFFFu) + 1u);
-                }
-            std::sort(lo.begin(), lo.end());
-            lo.erase(std::unique(lo.begin(), lo.end()), lo.end());
-            if (lo.back() == 65536u) lo.pop_back();
-        }
-        E.port_lo_valid = true;
-    }
-    return E.port_lo[protocol];
-}
-
-// argument checks shared by pg_reach_ports and its host twin: PG_OK with *empty set when there is
-// nothing to do, else *lo = the partition the call runs on
-int ports_args(pg_ctx* ctx, const pg_port_sweep_spec* spec, const uint32_t* out_codes, bool* empty,
-               std::vector<uint32_t>* lo) {
-    if (!ctx || !spec || !out_codes) return PG_EINVAL;
-    if (spec->protocol != PG_PROTO_TCP && spec->protocol != PG_PROTO_UDP)
-        return fail(ctx, PG_EINVAL, "a port sweep takes PG_PROTO_TCP or PG_PROTO_UDP");
-    if (spec->n_src > kReachMaxSide || spec->n_dst > kReachMaxSide) return fail(ctx, PG_EINVAL, "a side longer than 2^20");
-    *lo = port_bounds(ctx->eng, spec->protocol);
-    if (spec->n_intervals != lo->size())
-        return fail(ctx, PG_EINVAL, "n_intervals is " + std::to_string(spec->n_intervals) + " but the installed ACLs give " +
-                                        std::to_string(lo->size()) + " intervals: they changed since pg_port_intervals");
-    // (both sides <= 2^20 and row words <= 4097: the product fits 64 bits)
-    if ((uint64_t)spec->n_src * spec->n_dst * reach_row_words(lo->size()) >> 32)
-        return fail(ctx, PG_EINVAL, "n_src * n_dst * row_words(K) reaches 2^32");
-    *empty = !spec->n_src || !spec->n_dst;
-    if (!*empty && (!spec->src_ip || !spec->dst_ip)) return fail(ctx, PG_EINVAL, "null spec array");
-    return PG_OK;
-}
-
-struct HostPorts {
-    const W4 *rec_s, *rec_d;
-    const uint32_t *cls_s, *cls_d;  // form A
-    const W2* iv;
-    const uint32_t* len;
-    uint32_t K, n_src, n_dst;
-    uint32_t *codes, *open, *words;
-};
-// every pair, as k_ports_pairs runs it
-template <bool UNI, bool WIDE>
-void host_ports_pairs(const DevTableSet& T, const HostPorts& P) {
-    const uint64_t rw = reach_row_words(P.K);
-    const DevLoader img{T.node.img};
-    for (uint32_t i = 0; i < P.n_src; i++)
-        for (uint32_t j = 0; j < P.n_dst; j++) {
-            const uint64_t p = (uint64_t)i * P.n_dst + j;
-            auto emit_code = [&](uint32_t w, uint32_t word) { P.codes[p * rw + w] = word; };
-            auto emit_words = [&](uint32_t k0, const uint32_t(&o)[kReachQ], uint32_t valid) {
-                for (uint32_t q = 0; P.words && q < valid; q++) P.words[p * P.K + k0 + q] = o[q];
-            };
-            uint32_t open;
-            if constexpr (UNI)
-                open = ports_pair_uni<WIDE>(T, T.node, img, P.rec_s[i], P.cls_s[i], P.rec_d[j], P.cls_d[j], P.iv, P.len,
-                                            P.K, emit_code, emit_words);
-            else
-                open = ports_pair_tab(T, P.rec_s[i], P.rec_d[j], P.iv, P.len, P.K, emit_code, emit_words);
-            if (P.open) P.open[p] = open;
-        }
-}
-}  // namespace
-
-extern "C" {
-
-int pg_port_intervals(pg_ctx* ctx, int protocol, uint32_t* lo, size_t cap) {
-    if (!ctx) return PG_EINVAL;
-    GUARD_BEGIN
-    if (protocol != PG_PROTO_TCP && protocol != PG_PROTO_UDP)
-        return fail(ctx, PG_EINVAL, "port intervals exist for PG_PROTO_TCP and PG_PROTO_UDP");
-    const std::vector<uint32_t>& b = port_bounds(ctx->eng, protocol);
-    if (lo) std::copy(b.begin(), b.begin() + std::min(cap, b.size()), lo);
-    return (int)b.size();
-    GUARD_END(ctx)
-}
-
-int pg_reach_ports(pg_ctx* ctx, const pg_port_sweep_spec* spec, uint32_t* out_codes, uint32_t* out_open,
-                   uint32_t* out_words, void* stream) {
-    GUARD_BEGIN
-    bool empty = false;
-    std::vector<uint32_t> lo;
-    if (int rc = ports_args(ctx, spec, out_codes, &empty, &lo)) return rc;
-    if (empty) return PG_OK;
-    DEVICE_GUARD(ctx);
-    int rc = ctx->eng.sync();
-    if (rc) return rc;
-    const DevTableSet& T = *ctx->eng.view();
-    const PortsSpecDev sd{spec->src_ip, spec->dst_ip, lo.data(), (uint32_t)spec->n_src, (uint32_t)spec->n_dst,
-                          (uint32_t)lo.size(), (uint32_t)spec->protocol, spec->src_port};
-    std::string err;
-    if (dev_reach_ports(T, ctx->eng.tune, sd, out_codes, out_open, out_words, stream, &err) != 0 ||
-        dev_mark_use(ctx->eng.cur, stream, false, &err) != 0)
-        return fail(ctx, PG_EIO, err);
-    return PG_OK;
-    GUARD_END(ctx)
-}
-
-int pg_debug_reach_ports_host(pg_ctx* ctx, const pg_port_sweep_spec* spec, uint32_t* out_codes, uint32_t* out_open,
-                              uint32_t* out_words, int flags) {
-    GUARD_BEGIN
-    bool empty = false;
-    std::vector<uint32_t> lo;
-    if (int rc = ports_args(ctx, spec, out_codes, &empty, &lo)) return rc;
-    if (empty) return PG_OK;
-    Engine& E = ctx->eng;
-    if (!E.compiled) E.compile();
-    const DevTableSet T = host_view(E.host);
-    const uint32_t ns = (uint32_t)spec->n_src, nd = (uint32_t)spec->n_dst, K = (uint32_t)lo.size(), ne = ns + nd;
-    const bool form_a = (flags & 1) && reach_form_a(T.node, E.tune);
-    auto ip_of = [&](uint32_t e) { return e < ns ? spec->src_ip[e] : spec->dst_ip[e - ns]; };
-    std::vector<W4> rec(ne);
-    std::vector<uint32_t> cls(ne), len(K);
-    std::vector<W2> iv(K);
-    const DevLoader img{T.node.img};
-    for (uint32_t e = 0; e < ne; e++) {
-        if (form_a) reach_end_uni(T.node, img, ip_of(e), &rec[e], &cls[e]);
-        else rec[e] = reach_end_tab(T, ip_of(e));
-    }
-    for (uint32_t k = 0; k < K; k++) {
-        const W4 s = reach_service(spec->protocol, spec->src_port, lo[k]);
-        iv[k] = form_a ? reach_svc_uni(T.node, img, s) : reach_svc_tab(s);
-        len[k] = ports_len(lo.data(), K, k);
-    }
-    const HostPorts P{rec.data(), rec.data() + ns, cls.data(), cls.data() + ns, iv.data(), len.data(), K, ns, nd,
-                      out_codes, out_open, out_words};
-    if (!form_a) host_ports_pairs<false, false>(T, P);
-    else if (T.node.wide) host_ports_pairs<true, true>(T, P);
-    else host_ports_pairs<true, false>(T, P);
-    return PG_OK;
-    GUARD_END(ctx)
-}
-
-}  // extern "C"
-
-// ---- reachability diff (diff.hpp) ----------------------------------------------------------------
-namespace {
-static_assert(sizeof(pg_reach_change) == sizeof(DiffEntry), "pg_reach_change is diff.hpp's DiffEntry");
-
-// argument checks shared by pg_reach_diff and its host twin: PG_OK with *empty set when there is no
-// row (then *n_changes and trans are zeroed here)
-int diff_args(pg_ctx* ctx, const pg_reach_diff_spec* spec, uint64_t* n_changes, uint64_t* trans, bool* empty) {
-    if (!ctx) return PG_EINVAL;
-    if (!spec || !spec->before || !spec->after || !n_changes)
-        return fail(ctx, PG_EINVAL, "null spec, before, after or n_changes");
-    if (!spec->n_cols || spec->n_cols > kDiffMaxCols) return fail(ctx, PG_EINVAL, "n_cols is 0 or above 2^20");
-    if (spec->n_rows >> 32) return fail(ctx, PG_EINVAL, "n_rows reaches 2^32");
-    // (n_rows < 2^32 and row_words <= 2^16: the product fits 64 bits)
-    if (spec->n_rows * reach_row_words(spec->n_cols) >> 32) return fail(ctx, PG_EINVAL, "n_rows * row_words reaches 2^32");
-    *empty = !spec->n_rows;
-    if (*empty) {
-        *n_changes = 0;
-        if (trans) std::fill(trans, trans + 16, (uint64_t)0);
-    }
-    return PG_OK;
-}
-}  // namespace
-
-extern "C" {
-
-int pg_reach_diff(pg_ctx* ctx, const pg_reach_diff_spec* spec, pg_reach_change* changes, uint32_t* row_changes,
-                  uint64_t* n_changes, uint64_t* trans, void* stream) {
-    GUARD_BEGIN
-    bool empty = false;
-    if (int rc = diff_args(ctx, spec, n_changes, trans, &empty)) return rc;
-    if (empty) return PG_OK;
-    DEVICE_GUARD(ctx);
-    const DiffSpecDev sd{spec->before, spec->after, (uint32_t)spec->n_rows, spec->n_cols, spec->transitions, spec->cap};
-    std::string err;
-    if (dev_reach_diff(ctx->eng.tune.blocks_per_cu, sd, reinterpret_cast<DiffEntry*>(changes), row_changes, n_changes, trans,
-                       stream, &err) != 0)
-        return fail(ctx, PG_EIO, err);
-    return PG_OK;
-    GUARD_END(ctx)
-}
-
-int pg_debug_reach_diff_host(pg_ctx* ctx, const pg_reach_diff_spec* spec, pg_reach_change* changes,
-                             uint32_t* row_changes, uint64_t* n_changes, uint64_t* trans) {
-    GUARD_BEGIN
-    bool empty = false;
-    if (int rc = diff_args(ctx, spec, n_changes, trans, &empty)) return rc;
-    if (empty) return PG_OK;
-    const uint32_t rw = (uint32_t)reach_row_words(spec->n_cols), n_rows = (uint32_t)spec->n_rows;
-    const uint64_t cap = changes ? spec->cap : 0;
-    uint64_t n = 0, hist[16] = {0};
-    // every word in order, as the kernels' lanes run it
-    for (uint32_t row = 0; row < n_rows; row++) {
-        uint32_t in_row = 0;
-        for (uint32_t jw = 0; jw < rw; jw++) {
-            const uint32_t b = spec->before[(uint64_t)row * rw + jw], a = spec->after[(uint64_t)row * rw + jw];
-            const uint32_t valid = diff_valid(spec->n_cols, jw);
-            const DiffEq eb = diff_eq(b), ea = diff_eq(a);
-            uint32_t h[16] = {0};
-            if (b == a) diff_hist_same(eb, valid, h);
-            else diff_hist(eb, ea, valid, h);
-            for (int k = 0; k < 16; k++) hist[k] += h[k];
-            for (uint32_t m = diff_selected(eb, ea, b ^ a, valid, spec->transitions); m; m &= m - 1u) {
-                if (n < cap) changes[n] = pg_reach_change{row, diff_cell(jw, (uint32_t)__builtin_ctz(m), b, a)};
-                n++, in_row++;
-            }
-        }
-        if (row_changes) row_changes[row] = in_row;
-    }
-    *n_changes = n;
-    if (trans) std::copy(hist, hist + 16, trans);
-    return PG_OK;
-    GUARD_END(ctx)
-}
-
-int pg_debug_reach_diff_plan(pg_ctx* ctx, uint64_t n_words, uint32_t* tile_words, uint32_t* grid, uint64_t* chunk_words) {
-    if (!ctx || !tile_words || !grid || !chunk_words) return PG_EINVAL;
-    GUARD_BEGIN
-    DEVICE_GUARD(ctx);
-    const DiffPlan p = dev_diff_plan(n_words, ctx->eng.tune.blocks_per_cu);
-    *tile_words = p.tile_words, *grid = p.grid, *chunk_words = p.chunk_words;
     return PG_OK;
     GUARD_END(ctx)
 }

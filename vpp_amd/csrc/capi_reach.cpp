@@ -1,0 +1,362 @@
+// extern "C" boundary of the reachability audits (include/policygpu.h): the matrix, the port sweep
+// and the diff, each with the host twin the tests compare its kernels to.
+#include <algorithm>
+#include <numeric>
+
+#include "capi_internal.hpp"
+#include "diff.hpp"
+#include "ports.hpp"
+
+using namespace pg;
+
+// ---- reachability matrix (reach.hpp) -------------------------------------------------------------
+namespace {
+// argument checks shared by pg_reach_matrix and its host twin: PG_OK with *empty set when there
+// is nothing to do
+int reach_args(pg_ctx* ctx, const pg_reach_spec* spec, const uint32_t* out_packed, bool* empty) {
+    if (!ctx || !spec || !out_packed) return PG_EINVAL;
+    if (spec->n_src > kReachMaxSide || spec->n_dst > kReachMaxSide) return fail(ctx, PG_EINVAL, "a side longer than 2^20");
+    if (spec->n_svc > kReachMaxSvc) return fail(ctx, PG_EINVAL, "more than 4096 services");
+    *empty = !spec->n_src || !spec->n_dst || !spec->n_svc;
+    if (!*empty && (!spec->src_ip || !spec->dst_ip || !spec->services)) return fail(ctx, PG_EINVAL, "null spec array");
+    return PG_OK;
+}
+std::vector<W4> reach_services(const pg_reach_spec* spec) {
+    std::vector<W4> v(spec->n_svc);
+    for (size_t k = 0; k < spec->n_svc; k++)
+        v[k] = reach_service(spec->services[k].protocol, spec->services[k].src_port, spec->services[k].dst_port);
+    return v;
+}
+
+// The hoisted arrays of the host twins, and one form's prologue over them as k_reach_ends and
+// k_reach_svcs run it: rec (and cls, form A) of the end points src ++ dst, g[v] of the services in
+// `list`.
+struct HostHoist {
+    std::vector<W4> rec;
+    std::vector<uint32_t> cls;
+    std::vector<W2> g;
+    // spec: src_ip, dst_ip, n_src, n_dst. -> the form's end-point arrays
+    template <class SPEC>
+    ReachEnds run(bool uni, const DevTableSet& T, const SPEC& spec, const std::vector<W4>& svc,
+                  const std::vector<uint32_t>& list) {
+        const uint32_t ns = (uint32_t)spec.n_src, nd = (uint32_t)spec.n_dst;
+        const DevLoader img{T.node.img};
+        rec.resize(ns + nd), cls.resize(ns + nd), g.resize(svc.size());
+        for (uint32_t e = 0; e < ns + nd; e++) {
+            const uint32_t ip = e < ns ? spec.src_ip[e] : spec.dst_ip[e - ns];
+            if (uni) reach_end_uni(T.node, img, ip, &rec[e], &cls[e]);
+            else rec[e] = reach_end_tab(T, ip);
+        }
+        for (uint32_t v : list) g[v] = uni ? reach_svc_uni(T.node, img, svc[v]) : reach_svc_tab(svc[v]);
+        const uint32_t* c = uni ? cls.data() : nullptr;
+        return ReachEnds{rec.data(), rec.data() + ns, c, uni ? c + ns : nullptr, ns, nd};
+    }
+};
+
+// every word of the services `list` (one form's), as k_reach_pairs runs them
+template <bool UNI, bool WIDE>
+void host_reach_pairs(const DevTableSet& T, const ReachPass& P) {
+    const uint64_t rw = reach_row_words(P.n_dst);
+    const DevLoader img{T.node.img};
+    for (uint32_t k = 0; k < P.n_list; k++) {
+        const uint32_t v = P.svc_list[k];
+        for (uint32_t i = 0; i < P.n_src; i++) {
+            const uint64_t row = (uint64_t)v * P.n_src + i;
+            for (uint64_t jw = 0; jw < rw; jw++) {
+                const uint32_t j0 = (uint32_t)jw * kReachWordPairs;
+                uint32_t* ow = P.out_words ? P.out_words + row * P.n_dst + j0 : nullptr;
+                auto emit = [&](uint32_t r, const uint32_t(&o)[kReachQ], uint32_t valid) {
+                    for (uint32_t q = 0; ow && q < valid; q++) ow[r * kReachQ + q] = o[q];
+                };
+                uint32_t packed;
+                if constexpr (UNI)
+                    packed = reach_word_uni<WIDE>(T, T.node, img, P.rec_s[i], P.cls_s[i], P.rec_d, P.cls_d, j0, P.n_dst,
+                                                  P.svc[v], emit);
+                else
+                    packed = reach_word_tab(T, P.rec_s[i], P.rec_d, j0, P.n_dst, P.svc[v], emit);
+                P.out_packed[row * rw + jw] = packed;
+            }
+        }
+    }
+}
+}  // namespace
+
+extern "C" {
+
+size_t pg_reach_row_words(size_t n_dst) { return (size_t)reach_row_words(n_dst); }
+
+int pg_reach_matrix(pg_ctx* ctx, const pg_reach_spec* spec, uint32_t* out_packed, uint32_t* out_words,
+                    void* stream) {
+    bool empty = false;
+    if (int rc = reach_args(ctx, spec, out_packed, &empty)) return rc;
+    if (empty) return PG_OK;
+    DEVICE_GUARD(ctx);
+    GUARD_BEGIN
+    int rc = ctx->eng.sync();
+    if (rc) return rc;
+    const DevTableSet& T = *ctx->eng.view();
+    const std::vector<W4> svc = reach_services(spec);
+    const ReachSpecDev sd{spec->src_ip, spec->dst_ip, svc.data(), (uint32_t)spec->n_src, (uint32_t)spec->n_dst,
+                          (uint32_t)spec->n_svc};
+    std::string err;
+    if (dev_reach_matrix(T, ctx->eng.tune, sd, out_packed, out_words, stream, &err) != 0 ||
+        dev_mark_use(ctx->eng.cur, stream, false, &err) != 0)
+        return fail(ctx, PG_EIO, err);
+    return PG_OK;
+    GUARD_END(ctx)
+}
+
+int pg_debug_reach_matrix_host(pg_ctx* ctx, const pg_reach_spec* spec, uint32_t* out_packed, uint32_t* out_words,
+                               int flags) {
+    bool empty = false;
+    if (int rc = reach_args(ctx, spec, out_packed, &empty)) return rc;
+    GUARD_BEGIN
+    if (empty) return PG_OK;
+    Engine& E = ctx->eng;
+    if (!E.compiled) E.compile();
+    const DevTableSet T = host_view(E.host);
+    const uint32_t nv = (uint32_t)spec->n_svc;
+    const std::vector<W4> svc = reach_services(spec);
+    const bool form_a = (flags & 1) && reach_form_a(T.node, E.tune);
+    std::vector<uint32_t> la, lb;  // the services of each form
+    for (uint32_t v = 0; v < nv; v++) (form_a && svc[v].x <= 2u ? la : lb).push_back(v);
+    HostHoist H;
+    if (!la.empty()) {
+        const ReachEnds ends = H.run(true, T, *spec, svc, la);
+        const ReachPass P{ends, H.g.data(), la.data(), (uint32_t)la.size(), out_packed, out_words};
+        if (T.node.wide) host_reach_pairs<true, true>(T, P);
+        else host_reach_pairs<true, false>(T, P);
+    }
+    if (!lb.empty()) {
+        const ReachEnds ends = H.run(false, T, *spec, svc, lb);
+        const ReachPass P{ends, H.g.data(), lb.data(), (uint32_t)lb.size(), out_packed, out_words};
+        host_reach_pairs<false, false>(T, P);
+    }
+    return PG_OK;
+    GUARD_END(ctx)
+}
+
+}  // extern "C"
+
+// ---- port sweep (ports.hpp) ----------------------------------------------------------------------
+namespace {
+// The elementary dst-port intervals of a protocol: 0 and, of every installed rule whose L4 section
+// of that protocol carries a dst range, the two bounds as evalACL compares them (after its uint16
+// truncation, aclengine_mock.go:589): lower & 0xFFFF and (upper & 0xFFFF) + 1. Rules that never
+// reach the comparison (a structural FAILURE before it, an empty range) only add cuts. Both
+// protocols' bounds are kept with the engine until the next ACL change (Engine::touch).
+const std::vector<uint32_t>& port_bounds(Engine& E, int protocol) {
+    if (!E.port_lo_valid) {
+        for (int p : {PG_PROTO_TCP, PG_PROTO_UDP}) {
+            std::vector<uint32_t>& lo = E.port_lo[p];
+            lo.assign(1, 0u);
+            for (const auto& kv : E.by_name)
+                for (const AclRule& r : kv.second->rules) {
+                    const L4Section& s = p == PG_PROTO_TCP ? r.tcp : r.udp;
+                    if (!s.present || !s.has_dst) continue;
+                    lo.push_back(s.dst.lower & 0xFFFFu);
+                    lo.push_back((s.dst.upper & 0xFFFFu) + 1u);
+                }
+            std::sort(lo.begin(), lo.end());
+            lo.erase(std::unique(lo.begin(), lo.end()), lo.end());
+            if (lo.back() == 65536u) lo.pop_back();
+        }
+        E.port_lo_valid = true;
+    }
+    return E.port_lo[protocol];
+}
+
+// argument checks shared by pg_reach_ports and its host twin: PG_OK with *empty set when there is
+// nothing to do, else *lo = the partition the call runs on
+int ports_args(pg_ctx* ctx, const pg_port_sweep_spec* spec, const uint32_t* out_codes, bool* empty,
+               std::vector<uint32_t>* lo) {
+    if (!ctx || !spec || !out_codes) return PG_EINVAL;
+    if (spec->protocol != PG_PROTO_TCP && spec->protocol != PG_PROTO_UDP)
+        return fail(ctx, PG_EINVAL, "a port sweep takes PG_PROTO_TCP or PG_PROTO_UDP");
+    if (spec->n_src > kReachMaxSide || spec->n_dst > kReachMaxSide) return fail(ctx, PG_EINVAL, "a side longer than 2^20");
+    *lo = port_bounds(ctx->eng, spec->protocol);
+    if (spec->n_intervals != lo->size())
+        return fail(ctx, PG_EINVAL, "n_intervals is " + std::to_string(spec->n_intervals) + " but the installed ACLs give " +
+                                        std::to_string(lo->size()) + " intervals: they changed since pg_port_intervals");
+    // (both sides <= 2^20 and row words <= 4097: the product fits 64 bits)
+    if ((uint64_t)spec->n_src * spec->n_dst * reach_row_words(lo->size()) >> 32)
+        return fail(ctx, PG_EINVAL, "n_src * n_dst * row_words(K) reaches 2^32");
+    *empty = !spec->n_src || !spec->n_dst;
+    if (!*empty && (!spec->src_ip || !spec->dst_ip)) return fail(ctx, PG_EINVAL, "null spec array");
+    return PG_OK;
+}
+
+// every pair, as k_ports_pairs runs it
+template <bool UNI, bool WIDE>
+void host_ports_pairs(const DevTableSet& T, const ReachEnds& E, const W2* iv, const uint32_t* len, uint32_t K,
+                      uint32_t* codes, uint32_t* open_ports, uint32_t* words) {
+    const uint64_t rw = reach_row_words(K);
+    const DevLoader img{T.node.img};
+    for (uint32_t i = 0; i < E.n_src; i++)
+        for (uint32_t j = 0; j < E.n_dst; j++) {
+            const uint64_t p = (uint64_t)i * E.n_dst + j;
+            auto emit_code = [&](uint32_t w, uint32_t word) { codes[p * rw + w] = word; };
+            auto emit_words = [&](uint32_t k0, const uint32_t(&o)[kReachQ], uint32_t valid) {
+                for (uint32_t q = 0; words && q < valid; q++) words[p * K + k0 + q] = o[q];
+            };
+            uint32_t open;
+            if constexpr (UNI)
+                open = ports_pair_uni<WIDE>(T, T.node, img, E.rec_s[i], E.cls_s[i], E.rec_d[j], E.cls_d[j], iv, len, K,
+                                            emit_code, emit_words);
+            else
+                open = ports_pair_tab(T, E.rec_s[i], E.rec_d[j], iv, len, K, emit_code, emit_words);
+            if (open_ports) open_ports[p] = open;
+        }
+}
+}  // namespace
+
+extern "C" {
+
+int pg_port_intervals(pg_ctx* ctx, int protocol, uint32_t* lo, size_t cap) {
+    if (!ctx) return PG_EINVAL;
+    GUARD_BEGIN
+    if (protocol != PG_PROTO_TCP && protocol != PG_PROTO_UDP)
+        return fail(ctx, PG_EINVAL, "port intervals exist for PG_PROTO_TCP and PG_PROTO_UDP");
+    const std::vector<uint32_t>& b = port_bounds(ctx->eng, protocol);
+    if (lo) std::copy(b.begin(), b.begin() + std::min(cap, b.size()), lo);
+    return (int)b.size();
+    GUARD_END(ctx)
+}
+
+int pg_reach_ports(pg_ctx* ctx, const pg_port_sweep_spec* spec, uint32_t* out_codes, uint32_t* out_open,
+                   uint32_t* out_words, void* stream) {
+    GUARD_BEGIN
+    bool empty = false;
+    std::vector<uint32_t> lo;
+    if (int rc = ports_args(ctx, spec, out_codes, &empty, &lo)) return rc;
+    if (empty) return PG_OK;
+    DEVICE_GUARD(ctx);
+    int rc = ctx->eng.sync();
+    if (rc) return rc;
+    const DevTableSet& T = *ctx->eng.view();
+    const PortsSpecDev sd{spec->src_ip, spec->dst_ip, lo.data(), (uint32_t)spec->n_src, (uint32_t)spec->n_dst,
+                          (uint32_t)lo.size(), (uint32_t)spec->protocol, spec->src_port};
+    std::string err;
+    if (dev_reach_ports(T, ctx->eng.tune, sd, out_codes, out_open, out_words, stream, &err) != 0 ||
+        dev_mark_use(ctx->eng.cur, stream, false, &err) != 0)
+        return fail(ctx, PG_EIO, err);
+    return PG_OK;
+    GUARD_END(ctx)
+}
+
+int pg_debug_reach_ports_host(pg_ctx* ctx, const pg_port_sweep_spec* spec, uint32_t* out_codes, uint32_t* out_open,
+                              uint32_t* out_words, int flags) {
+    GUARD_BEGIN
+    bool empty = false;
+    std::vector<uint32_t> lo;
+    if (int rc = ports_args(ctx, spec, out_codes, &empty, &lo)) return rc;
+    if (empty) return PG_OK;
+    Engine& E = ctx->eng;
+    if (!E.compiled) E.compile();
+    const DevTableSet T = host_view(E.host);
+    const uint32_t K = (uint32_t)lo.size();
+    const bool form_a = (flags & 1) && reach_form_a(T.node, E.tune);
+    // the K representatives as services, all of one form
+    std::vector<W4> svc(K);
+    std::vector<uint32_t> list(K), len(K);
+    std::iota(list.begin(), list.end(), 0u);
+    for (uint32_t k = 0; k < K; k++) {
+        svc[k] = reach_service(spec->protocol, spec->src_port, lo[k]);
+        len[k] = ports_len(lo.data(), K, k);
+    }
+    HostHoist H;
+    const ReachEnds ends = H.run(form_a, T, *spec, svc, list);
+    if (!form_a) host_ports_pairs<false, false>(T, ends, H.g.data(), len.data(), K, out_codes, out_open, out_words);
+    else if (T.node.wide) host_ports_pairs<true, true>(T, ends, H.g.data(), len.data(), K, out_codes, out_open, out_words);
+    else host_ports_pairs<true, false>(T, ends, H.g.data(), len.data(), K, out_codes, out_open, out_words);
+    return PG_OK;
+    GUARD_END(ctx)
+}
+
+}  // extern "C"
+
+// ---- reachability diff (diff.hpp) ----------------------------------------------------------------
+namespace {
+static_assert(sizeof(pg_reach_change) == sizeof(DiffEntry), "pg_reach_change is diff.hpp's DiffEntry");
+
+// argument checks shared by pg_reach_diff and its host twin: PG_OK with *empty set when there is no
+// row (then *n_changes and trans are zeroed here)
+int diff_args(pg_ctx* ctx, const pg_reach_diff_spec* spec, uint64_t* n_changes, uint64_t* trans, bool* empty) {
+    if (!ctx) return PG_EINVAL;
+    if (!spec || !spec->before || !spec->after || !n_changes)
+        return fail(ctx, PG_EINVAL, "null spec, before, after or n_changes");
+    if (!spec->n_cols || spec->n_cols > kDiffMaxCols) return fail(ctx, PG_EINVAL, "n_cols is 0 or above 2^20");
+    if (spec->n_rows >> 32) return fail(ctx, PG_EINVAL, "n_rows reaches 2^32");
+    // (n_rows < 2^32 and row_words <= 2^16: the product fits 64 bits)
+    if (spec->n_rows * reach_row_words(spec->n_cols) >> 32) return fail(ctx, PG_EINVAL, "n_rows * row_words reaches 2^32");
+    *empty = !spec->n_rows;
+    if (*empty) {
+        *n_changes = 0;
+        if (trans) std::fill(trans, trans + 16, (uint64_t)0);
+    }
+    return PG_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int pg_reach_diff(pg_ctx* ctx, const pg_reach_diff_spec* spec, pg_reach_change* changes, uint32_t* row_changes,
+                  uint64_t* n_changes, uint64_t* trans, void* stream) {
+    GUARD_BEGIN
+    bool empty = false;
+    if (int rc = diff_args(ctx, spec, n_changes, trans, &empty)) return rc;
+    if (empty) return PG_OK;
+    DEVICE_GUARD(ctx);
+    const DiffSpecDev sd{spec->before, spec->after, (uint32_t)spec->n_rows, spec->n_cols, spec->transitions, spec->cap};
+    std::string err;
+    if (dev_reach_diff(ctx->eng.tune.blocks_per_cu, sd, reinterpret_cast<DiffEntry*>(changes), row_changes, n_changes, trans,
+                       stream, &err) != 0)
+        return fail(ctx, PG_EIO, err);
+    return PG_OK;
+    GUARD_END(ctx)
+}
+
+int pg_debug_reach_diff_host(pg_ctx* ctx, const pg_reach_diff_spec* spec, pg_reach_change* changes,
+                             uint32_t* row_changes, uint64_t* n_changes, uint64_t* trans) {
+    GUARD_BEGIN
+    bool empty = false;
+    if (int rc = diff_args(ctx, spec, n_changes, trans, &empty)) return rc;
+    if (empty) return PG_OK;
+    const uint32_t rw = (uint32_t)reach_row_words(spec->n_cols), n_rows = (uint32_t)spec->n_rows;
+    const uint64_t cap = changes ? spec->cap : 0;
+    uint64_t n = 0, hist[16] = {0};
+    // every word in order, as the kernels' lanes run it
+    for (uint32_t row = 0; row < n_rows; row++) {
+        uint32_t in_row = 0;
+        for (uint32_t jw = 0; jw < rw; jw++) {
+            const uint32_t b = spec->before[(uint64_t)row * rw + jw], a = spec->after[(uint64_t)row * rw + jw];
+            const uint32_t valid = diff_valid(spec->n_cols, jw);
+            const DiffEq eb = diff_eq(b), ea = diff_eq(a);
+            uint32_t h[16] = {0};
+            if (b == a) diff_hist_same(eb, valid, h);
+            else diff_hist(eb, ea, valid, h);
+            for (int k = 0; k < 16; k++) hist[k] += h[k];
+            for (uint32_t m = diff_selected(eb, ea, b ^ a, valid, spec->transitions); m; m &= m - 1u) {
+                if (n < cap) changes[n] = pg_reach_change{row, diff_cell(jw, (uint32_t)__builtin_ctz(m), b, a)};
+                n++, in_row++;
+            }
+        }
+        if (row_changes) row_changes[row] = in_row;
+    }
+    *n_changes = n;
+    if (trans) std::copy(hist, hist + 16, trans);
+    return PG_OK;
+    GUARD_END(ctx)
+}
+
+int pg_debug_reach_diff_plan(pg_ctx* ctx, uint64_t n_words, uint32_t* tile_words, uint32_t* grid, uint64_t* chunk_words) {
+    if (!ctx || !tile_words || !grid || !chunk_words) return PG_EINVAL;
+    GUARD_BEGIN
+    DEVICE_GUARD(ctx);
+    const DiffPlan p = dev_diff_plan(n_words, ctx->eng.tune.blocks_per_cu);
+    *tile_words = p.tile_words, *grid = p.grid, *chunk_words = p.chunk_words;
+    return PG_OK;
+    GUARD_END(ctx)
+}
+
+}  // extern "C"

@@ -22,7 +22,6 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
-#include <atomic>
 #include <type_traits>
 #include <cstdio>
 #include <cstdlib>
@@ -30,17 +29,9 @@
 #include <utility>
 
 #include "classify.hpp"
+#include "hiputil.hpp"
 
 namespace pg {
-
-#define HIPCHK(expr)                                                         \
-    do {                                                                     \
-        hipError_t e_ = (expr);                                              \
-        if (e_ != hipSuccess) {                                              \
-            if (err) *err = std::string(#expr ": ") + hipGetErrorString(e_); \
-            return -1;                                                       \
-        }                                                                    \
-    } while (0)
 
 struct DeviceBuffers {
     void* blob = nullptr;
@@ -1183,40 +1174,17 @@ __global__ void k_conn_queries(DevTableSet T, const ConnQueryDev* q, uint32_t n,
 // per CU), block_stage (workgroup size of LDS-staged launches; 0 = per mode).
 // (kCommonStageExtraWords, device.hpp: the common-row section may take the image past the base cap)
 
-// CUs of the current device (per device: contexts on different GPUs share the process)
-static uint32_t num_cus() {
-    constexpr int kMaxDev = 64;
-    static std::atomic<uint32_t> cus[kMaxDev] = {};  // contexts on several threads may launch at once
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) return 256;
-    uint32_t c = cus[dev].load(std::memory_order_relaxed);
-    if (!c) {
-        hipDeviceProp_t p;
-        c = (hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0) ? (uint32_t)p.multiProcessorCount
-                                                                                       : 256u;
-        cus[dev].store(c, std::memory_order_relaxed);
-    }
-    return c;
-}
-
 static int grid_for(uint64_t items, uint32_t blocks_per_cu = 0) {
     const uint32_t bpc = blocks_per_cu ? blocks_per_cu : 4u;
     uint64_t g = (items + kBlock - 1) / kBlock;
     return (int)std::max<uint64_t>(1, std::min<uint64_t>(g, (uint64_t)num_cus() * bpc));
 }
 
-// Grid of a grid-stride classify kernel: exactly the workgroups that are resident at once
-// (registers / LDS of this instantiation), so no workgroup waits for another to finish, capped
-// by the work and by blocks_per_cu when set.
+// grid_resident (hiputil.hpp) of a classify kernel, traced under PG_DEBUG_LAUNCH
 template <class K>
-static int grid_resident(K kernel, int bs, size_t lds, uint64_t items, uint32_t blocks_per_cu) {
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, bs, lds) != hipSuccess || per_cu < 1)
-        per_cu = 1;
-    const int occ = per_cu;
-    if (blocks_per_cu) per_cu = std::min<int>(per_cu, (int)blocks_per_cu);
-    const uint64_t g = (items + bs - 1) / bs;
-    const int grid = (int)std::max<uint64_t>(1, std::min<uint64_t>(g, (uint64_t)num_cus() * per_cu));
+static int grid_classify(K kernel, int bs, size_t lds, uint64_t items, uint32_t blocks_per_cu) {
+    int occ = 0;
+    const int grid = grid_resident(kernel, bs, lds, items, blocks_per_cu, &occ);
     static const bool dbg = std::getenv("PG_DEBUG_LAUNCH") != nullptr;  // measurement aid: launch geometry
     if (dbg) std::fprintf(stderr, "pg launch: block %d, LDS %zu B, occupancy %d blocks/CU, grid %d\n", bs, lds, occ, grid);
     return grid;
@@ -1238,7 +1206,7 @@ static void launch_bs(const DevTableSet& T, const Tuning& tu, int t, const uint3
     // ANY-protocol packets (PG_CONN_DEFER_ANY, PG_POD_DEFER_ANY; the launch's mark word and
     // number: dev_classify)
     constexpr bool defer = NODE && (STAGE & 32) && (STAGE & 64) && defer_any<MODE>();
-    hipLaunchKernelGGL(k, dim3(grid_resident(k, BS, lds, items, bpc)), dim3(BS), lds, st, T, t, src, dst, sport, dport,
+    hipLaunchKernelGGL(k, dim3(grid_classify(k, BS, lds, items, bpc)), dim3(BS), lds, st, T, t, src, dst, sport, dport,
                        proto, n, out, counters, stage, cells);
     if constexpr (defer && !PG_PROBE_NOANYLAUNCH) {  // (measurement build: -DPG_PROBE_NOANYLAUNCH=1 skips it)
         auto ka = k_node_any<MODE, COUNT>;
@@ -1472,7 +1440,7 @@ template <bool DST, bool SP>
 static void launch_probe(const Tuning& tu, const uint32_t* src, const uint32_t* dst, const uint16_t* sport,
                          const uint16_t* dport, const uint8_t* proto, uint64_t n, uint32_t* out, hipStream_t st) {
     auto k = k_stream_probe<DST, SP, 512>;
-    hipLaunchKernelGGL(k, dim3(grid_resident(k, 512, 0, (n + PG_TPL - 1) / PG_TPL, tu.blocks_per_cu)), dim3(512), 0,
+    hipLaunchKernelGGL(k, dim3(grid_classify(k, 512, 0, (n + PG_TPL - 1) / PG_TPL, tu.blocks_per_cu)), dim3(512), 0,
                        st, src, dst, sport, dport, proto, n, out);
 }
 

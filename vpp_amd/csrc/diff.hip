@@ -16,28 +16,21 @@
 // (VEC), four 4-B loads otherwise. Word -> (row, first column) is one 32-bit division per lane and
 // tile, then a carry.
 //
-// No kernel reads a table or touches a hit counter.
+// No kernel reads a table or touches a hit counter. (The driver's error macro, CU count, occupancy
+// query and scratch-block owner: hiputil.hpp.)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <string>
 
 #include "diff.hpp"
+#include "hiputil.hpp"
 
 namespace pg {
 
 namespace {
 
 constexpr uint32_t kDiffWaves = kDiffBlock / 64;
-
-#define DIFF_CHK(expr)                                                       \
-    do {                                                                     \
-        hipError_t e_ = (expr);                                              \
-        if (e_ != hipSuccess) {                                              \
-            if (err) *err = std::string(#expr ": ") + hipGetErrorString(e_); \
-            return -1;                                                       \
-        }                                                                    \
-    } while (0)
 
 // a lane's 4 words of both inputs, starting at word w0 < n_words; words past the end read as 0
 template <bool VEC>
@@ -203,21 +196,13 @@ __global__ __launch_bounds__(kDiffBlock) void k_diff_emit(const uint32_t* __rest
     }
 }
 
+// both passes run on one partition: the occupancy of the larger count kernel and of the emit kernel
 uint32_t diff_resident(uint32_t blocks_per_cu) {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
-        cus = 256;
-    // both passes run on one partition: the occupancy of the larger count kernel and of the emit kernel
-    int per_cu = 0, pe = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_diff_count<true, true, false>, kDiffBlock, 0) != hipSuccess ||
-        per_cu < 1)
-        per_cu = 1;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&pe, k_diff_emit<false>, kDiffBlock, 0) == hipSuccess && pe >= 1)
-        per_cu = std::min(per_cu, pe);
+    int per_cu = std::max(1, occupancy(k_diff_count<true, true, false>, kDiffBlock, 0));
+    if (const int pe = occupancy(k_diff_emit<false>, kDiffBlock, 0)) per_cu = std::min(per_cu, pe);
     (void)hipGetLastError();  // (a failed query is answered by the fall-back above)
     if (blocks_per_cu) per_cu = std::min<int>(per_cu, (int)blocks_per_cu);
-    return (uint32_t)cus * (uint32_t)per_cu;
+    return num_cus() * (uint32_t)per_cu;
 }
 
 template <bool HIST, bool ROWS>
@@ -245,45 +230,35 @@ int dev_reach_diff(uint32_t blocks_per_cu, const DiffSpecDev& spec, DiffEntry* c
     // one scratch block: [chunk counts, then bases, u64[grid] | total u64 | trans u64[16]]; the total
     // and the histogram come back in one copy
     const size_t n_back = 1 + (trans ? 16 : 0);
-    uint64_t* d = nullptr;
-    DIFF_CHK(hipMalloc(&d, ((size_t)p.grid + 17) * sizeof(uint64_t)));
+    Scratch blk;
+    if (Scratch::make(&blk, ((size_t)p.grid + 17) * sizeof(uint64_t), err) != 0) return -1;
+    uint64_t* d = blk.at<uint64_t>(0);
     uint64_t back[17] = {0};
-    auto run = [&]() -> int {
-        unsigned long long* dt = reinterpret_cast<unsigned long long*>(d + p.grid + 1);
-        if (trans) DIFF_CHK(hipMemsetAsync(dt, 0, 16 * sizeof(uint64_t), st));
-        if (row_changes) DIFF_CHK(hipMemsetAsync(row_changes, 0, (size_t)spec.n_rows * sizeof(uint32_t), st));
-        if (trans && row_changes) launch_count<true, true>(vec, p, st, spec.before, spec.after, S, d, dt, row_changes);
-        else if (trans) launch_count<true, false>(vec, p, st, spec.before, spec.after, S, d, dt, row_changes);
-        else if (row_changes) launch_count<false, true>(vec, p, st, spec.before, spec.after, S, d, dt, row_changes);
-        else launch_count<false, false>(vec, p, st, spec.before, spec.after, S, d, dt, row_changes);
-        hipLaunchKernelGGL(k_diff_scan, dim3(1), dim3(kDiffBlock), 0, st, d, p.grid);
-        DIFF_CHK(hipGetLastError());
-        DIFF_CHK(hipMemcpyAsync(back, d + p.grid, n_back * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-        DIFF_CHK(hipStreamSynchronize(st));
-        if (changes && spec.cap && back[0]) {
-            if (vec)
-                hipLaunchKernelGGL(k_diff_emit<true>, dim3(p.grid), dim3(kDiffBlock), 0, st, spec.before, spec.after, S,
-                                   p.chunk_words, d, spec.cap, changes);
-            else
-                hipLaunchKernelGGL(k_diff_emit<false>, dim3(p.grid), dim3(kDiffBlock), 0, st, spec.before, spec.after, S,
-                                   p.chunk_words, d, spec.cap, changes);
-            DIFF_CHK(hipGetLastError());
-        }
-        return 0;
-    };
-    const int rc = run();
-    // the emit pass has read the chunk bases before the block is released
-    const hipError_t es = hipStreamSynchronize(st);
-    (void)hipFree(d);
-    if (rc == 0 && es != hipSuccess) {
-        if (err) *err = std::string("reach diff: ") + hipGetErrorString(es);
-        return -1;
+    unsigned long long* dt = reinterpret_cast<unsigned long long*>(d + p.grid + 1);
+    if (trans) HIPCHK(hipMemsetAsync(dt, 0, 16 * sizeof(uint64_t), st));
+    if (row_changes) HIPCHK(hipMemsetAsync(row_changes, 0, (size_t)spec.n_rows * sizeof(uint32_t), st));
+    if (trans && row_changes) launch_count<true, true>(vec, p, st, spec.before, spec.after, S, d, dt, row_changes);
+    else if (trans) launch_count<true, false>(vec, p, st, spec.before, spec.after, S, d, dt, row_changes);
+    else if (row_changes) launch_count<false, true>(vec, p, st, spec.before, spec.after, S, d, dt, row_changes);
+    else launch_count<false, false>(vec, p, st, spec.before, spec.after, S, d, dt, row_changes);
+    hipLaunchKernelGGL(k_diff_scan, dim3(1), dim3(kDiffBlock), 0, st, d, p.grid);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(back, d + p.grid, n_back * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (changes && spec.cap && back[0]) {
+        if (vec)
+            hipLaunchKernelGGL(k_diff_emit<true>, dim3(p.grid), dim3(kDiffBlock), 0, st, spec.before, spec.after, S,
+                               p.chunk_words, d, spec.cap, changes);
+        else
+            hipLaunchKernelGGL(k_diff_emit<false>, dim3(p.grid), dim3(kDiffBlock), 0, st, spec.before, spec.after, S,
+                               p.chunk_words, d, spec.cap, changes);
+        HIPCHK(hipGetLastError());
     }
-    if (rc == 0) {
-        *n_changes = back[0];
-        if (trans) std::copy(back + 1, back + 17, trans);
-    }
-    return rc;
+    // (the emit pass reads the chunk bases in the block: Scratch)
+    if (blk.finish(st, "reach diff", err) != 0) return -1;
+    *n_changes = back[0];
+    if (trans) std::copy(back + 1, back + 17, trans);
+    return 0;
 }
 
 }  // namespace pg

@@ -5,7 +5,7 @@
 // For a fixed protocol (TCP or UDP) and src port, evalACL looks at a packet's dst port only through
 // the rules' dst-port ranges, so the verdict word of (src, dst, proto, sport, dport) is constant
 // inside every elementary interval of the partition of 0..65535 by all rules' dst-port bounds
-// (pg_port_intervals, capi.cpp). A sweep over all 65,536 ports is K evaluations per pair, on the
+// (pg_port_intervals, capi_reach.cpp). A sweep over all 65,536 ports is K evaluations per pair, on the
 // K representatives (proto, sport, lo[k]). The prologues are reach.hpp's: per end point
 // reach_end_uni / reach_end_tab, per interval reach_svc_uni / reach_svc_tab on the representative.
 //

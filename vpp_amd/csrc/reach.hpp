@@ -136,18 +136,23 @@ PG_HD uint32_t reach_word_tab(const DevTableSet& T, const W4& es1, const W4* end
     return packed;
 }
 
-// What a pair pass works on: the hoisted arrays of one form and the services it covers. A pass has
-// n_list * n_src * row_words words: word jw of src i of service v = svc_list[k] lands at
-// out_packed[(v * n_src + i) * row_words + jw], its full words at out_words[(v * n_src + i) * n_dst +
-// 16 * jw ...] (the kernel numbers them with i fastest, reach.hip).
-struct ReachPass {
+// The hoisted end-point arrays of one form, src and dst (the matrix's and the port sweep's).
+struct ReachEnds {
     const W4* rec_s;          // form A: class records; form B: ends {interface, tin, tout, address}
     const W4* rec_d;
     const uint32_t* cls_s;    // form A: classes
     const uint32_t* cls_d;
+    uint32_t n_src, n_dst;
+};
+
+// What a pair pass works on: the end points and the services it covers. A pass has
+// n_list * n_src * row_words words: word jw of src i of service v = svc_list[k] lands at
+// out_packed[(v * n_src + i) * row_words + jw], its full words at out_words[(v * n_src + i) * n_dst +
+// 16 * jw ...] (the kernel numbers them with i fastest, reach.hip).
+struct ReachPass : ReachEnds {
     const W2* svc;            // per service (all n_svc): form A {gs, ga}, form B {SYN key, SYN-ACK key}
     const uint32_t* svc_list; // the services of this pass
-    uint32_t n_list, n_src, n_dst;
+    uint32_t n_list;
     uint32_t* out_packed;
     uint32_t* out_words;      // null: not asked for
 };
