@@ -599,6 +599,57 @@ int pg_debug_reach_diff_host(pg_ctx* ctx, const pg_reach_diff_spec* spec, pg_rea
 int pg_debug_reach_diff_plan(pg_ctx* ctx, uint64_t n_words, uint32_t* tile_words, uint32_t* grid,
                              uint64_t* chunk_words);
 
+/* ---- reachability closure: multi-hop reach and hop counts, on the device -------------------
+ * "If this pod is compromised, what can the attacker get to by hopping through the pods it
+ * reaches, and in how many hops?" The input is a pg_reach_matrix out_packed taken with the SAME
+ * end-point list on both sides (n_src == n_dst == n), which stays on the device.
+ *   Edge: i -> j when some selected slice v holds PG_CONN_ALLOW in cell (v, i, j). Cell (i, i) is a
+ *   cell like any other: there is no implicit self-reach.
+ *   hops(i, j): the least k >= 1 for which a path of k edges leads from i to j; hops(i, i) is the
+ *   shortest cycle through i. Cell (i, j) is reachable when such a k exists and, with max_hops != 0,
+ *   k <= max_hops.
+ *   out_packed  device, required, n rows of pg_reach_row_words(n) words in the audits' layout:
+ *               PG_CONN_ALLOW in the reachable cells, PG_CONN_DENY_SYN in all others, the padding
+ *               bits of a row's last word zero. A valid before / after of pg_reach_diff with n_rows
+ *               = n_cols = n ("what did this change open transitively"). With max_hops = 1 it is the
+ *               one-hop graph.
+ *   out_hops    device, optional, n * n uint16_t, row-major: hops(i, j), 0 for cells that are not
+ *               reachable; every cell is written (n <= 2^15: the count always fits)
+ *   out_count   device, optional, n words: the reachable cells of each row -- the blast radius of
+ *               end point i
+ *   result      host, required
+ * The padding bits of the input rows are masked, never trusted. Duplicate end points are just equal
+ * rows and columns. Like pg_reach_diff the call reads no table and triggers no compile, and it
+ * never touches the hit counters or their snapshots; ctx only names the device and its launch
+ * knobs. It enqueues on hip_stream, one launch per level, and synchronises that stream, because the
+ * counts come back to the host. n == 0: PG_OK, *result zeroed, nothing else written. PG_EINVAL
+ * (pg_last_error says which): a null spec, matrix, out_packed or result; n above 2^15; n_svc 0 or
+ * above 4096. An all-zero svc_select is valid and gives the empty graph. PG_ENOMEM: the scratch
+ * allocation (four n x n bit matrices) failed. */
+typedef struct pg_reach_closure_spec {
+    const uint32_t* matrix;   /* device: n_svc * n rows of pg_reach_row_words(n) words */
+    uint32_t n;               /* end points, 1 .. 2^15 */
+    uint32_t n_svc;           /* slices of the matrix, 1 .. 4096 */
+    const uint8_t* svc_select;/* host, optional, n_svc bytes: non-zero = this slice contributes edges; NULL = all */
+    uint32_t max_hops;        /* 0 = until nothing new is found; k = paths of at most k edges */
+} pg_reach_closure_spec;
+typedef struct pg_reach_closure_result {   /* host */
+    uint32_t levels;          /* the largest hop count assigned to any cell (0: no edge) */
+    uint64_t n_edges;         /* cells of the one-hop graph */
+    uint64_t n_reachable;     /* cells of the closure */
+} pg_reach_closure_result;
+int pg_reach_closure(pg_ctx* ctx, const pg_reach_closure_spec* spec, uint32_t* out_packed, uint16_t* out_hops,
+                     uint32_t* out_count, pg_reach_closure_result* result, void* hip_stream);
+/* TESTS ONLY -- never on the audit path: pg_reach_closure's per-word code (closure.hpp, the
+ * functions the kernels call) on the host, level by level; matrix, out_packed, out_hops and
+ * out_count are host arrays. Does not touch the device. */
+int pg_debug_reach_closure_host(pg_ctx* ctx, const pg_reach_closure_spec* spec, uint32_t* out_packed, uint16_t* out_hops,
+                                uint32_t* out_count, pg_reach_closure_result* result);
+/* TESTS ONLY: how one level of a pg_reach_closure over n end points is cut, from the one function
+ * the launch itself uses (closure.hpp closure_plan): the rows and columns of the output a workgroup
+ * owns and the workgroups of a level. Launches nothing. */
+int pg_debug_reach_closure_plan(pg_ctx* ctx, uint32_t n, uint32_t* tile_rows, uint32_t* tile_cols, uint32_t* grid);
+
 /* ---- policy configurator ------------------------------------------
  * configurator.PolicyConfiguratorAPI / Txn (plugins/policy/configurator/configurator_api.go:28-54,
  * configurator_impl.go:104-472): K8s-shaped policies per pod -> ordered ContivRule lists

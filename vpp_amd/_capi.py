@@ -103,6 +103,15 @@ class pg_reach_diff_spec(C.Structure):
                 ("transitions", C.c_uint32), ("cap", C.c_uint64)]
 
 
+class pg_reach_closure_spec(C.Structure):
+    _fields_ = [("matrix", C.c_void_p), ("n", C.c_uint32), ("n_svc", C.c_uint32), ("svc_select", C.c_void_p),
+                ("max_hops", C.c_uint32)]
+
+
+class pg_reach_closure_result(C.Structure):
+    _fields_ = [("levels", C.c_uint32), ("n_edges", C.c_uint64), ("n_reachable", C.c_uint64)]
+
+
 class pg_pod_id(C.Structure):
     _fields_ = [("ns", C.c_char_p), ("name", C.c_char_p)]
 
@@ -254,6 +263,12 @@ _SIGS = {
     "pg_debug_reach_diff_host": (C.c_int, [_P, C.POINTER(pg_reach_diff_spec), _P, _P, C.POINTER(C.c_uint64), _P]),
     "pg_debug_reach_diff_plan": (C.c_int, [_P, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                            C.POINTER(C.c_uint64)]),
+    "pg_reach_closure": (C.c_int, [_P, C.POINTER(pg_reach_closure_spec), _P, _P, _P,
+                                   C.POINTER(pg_reach_closure_result), _P]),
+    "pg_debug_reach_closure_host": (C.c_int, [_P, C.POINTER(pg_reach_closure_spec), _P, _P, _P,
+                                              C.POINTER(pg_reach_closure_result)]),
+    "pg_debug_reach_closure_plan": (C.c_int, [_P, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                              C.POINTER(C.c_uint32)]),
     "pg_session_rules_new": (_P, [C.c_char_p]),
     "pg_session_rules_free": (None, [_P]),
     "pg_session_rules_clear": (C.c_int, [_P]),

@@ -1,9 +1,10 @@
-// extern "C" boundary of the reachability audits (include/policygpu.h): the matrix, the port sweep
-// and the diff, each with the host twin the tests compare its kernels to.
+// extern "C" boundary of the reachability audits (include/policygpu.h): the matrix, the port sweep,
+// the diff and the closure, each with the host twin the tests compare its kernels to.
 #include <algorithm>
 #include <numeric>
 
 #include "capi_internal.hpp"
+#include "closure.hpp"
 #include "diff.hpp"
 #include "ports.hpp"
 
@@ -357,6 +358,133 @@ int pg_debug_reach_diff_plan(pg_ctx* ctx, uint64_t n_words, uint32_t* tile_words
     *tile_words = p.tile_words, *grid = p.grid, *chunk_words = p.chunk_words;
     return PG_OK;
     GUARD_END(ctx)
+}
+
+}  // extern "C"
+
+// ---- reachability closure (closure.hpp) ----------------------------------------------------------
+namespace {
+static_assert(sizeof(pg_reach_closure_result) == sizeof(ClosureResult), "pg_reach_closure_result is closure.hpp's ClosureResult");
+
+// argument checks shared by pg_reach_closure and its host twin: PG_OK with *empty set when there is
+// no end point (then *result is zeroed here), else *list = the selected slices
+int closure_args(pg_ctx* ctx, const pg_reach_closure_spec* spec, const uint32_t* out_packed, pg_reach_closure_result* result,
+                 bool* empty, std::vector<uint32_t>* list) {
+    if (!ctx) return PG_EINVAL;
+    if (!spec || !spec->matrix || !out_packed || !result)
+        return fail(ctx, PG_EINVAL, "null spec, matrix, out_packed or result");
+    if (spec->n > kClosureMaxN) return fail(ctx, PG_EINVAL, "more than 2^15 end points");
+    if (!spec->n_svc || spec->n_svc > kClosureMaxSvc) return fail(ctx, PG_EINVAL, "n_svc is 0 or above 4096");
+    *empty = !spec->n;
+    if (*empty) *result = pg_reach_closure_result{0, 0, 0};
+    for (uint32_t v = 0; v < spec->n_svc; v++)
+        if (!spec->svc_select || spec->svc_select[v]) list->push_back(v);
+    return PG_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int pg_reach_closure(pg_ctx* ctx, const pg_reach_closure_spec* spec, uint32_t* out_packed, uint16_t* out_hops,
+                     uint32_t* out_count, pg_reach_closure_result* result, void* stream) {
+    GUARD_BEGIN
+    bool empty = false;
+    std::vector<uint32_t> list;
+    if (int rc = closure_args(ctx, spec, out_packed, result, &empty, &list)) return rc;
+    if (empty) return PG_OK;
+    DEVICE_GUARD(ctx);
+    const ClosureSpecDev sd{spec->matrix, spec->n, spec->n_svc, list.data(), (uint32_t)list.size(), spec->max_hops};
+    std::string err;
+    ClosureResult r{0, 0, 0};
+    const int rc = dev_reach_closure(sd, out_packed, out_hops, out_count, &r, stream, &err);
+    if (rc != 0) return fail(ctx, rc == -2 ? PG_ENOMEM : PG_EIO, err);
+    *result = pg_reach_closure_result{r.levels, r.n_edges, r.n_reachable};
+    return PG_OK;
+    GUARD_END(ctx)
+}
+
+int pg_debug_reach_closure_host(pg_ctx* ctx, const pg_reach_closure_spec* spec, uint32_t* out_packed, uint16_t* out_hops,
+                                uint32_t* out_count, pg_reach_closure_result* result) {
+    GUARD_BEGIN
+    bool empty = false;
+    std::vector<uint32_t> list;
+    if (int rc = closure_args(ctx, spec, out_packed, result, &empty, &list)) return rc;
+    if (empty) return PG_OK;
+    const uint32_t n = spec->n, stride = closure_stride(n), chunks = closure_bit_words(n), rw = (uint32_t)reach_row_words(n);
+    const size_t mat = (size_t)n * stride;
+    std::vector<uint32_t> A(mat), R(mat), F(mat), Fn(mat), acc(stride);
+    std::vector<uint8_t> live(n, 0), live_n(n);
+    if (out_hops) std::fill(out_hops, out_hops + (size_t)n * n, (uint16_t)0);
+    auto hops = [&](uint32_t i, uint32_t w, uint32_t bits, uint32_t level) {
+        for (; out_hops && bits; bits &= bits - 1u) out_hops[(size_t)i * n + 32u * w + (uint32_t)__builtin_ctz(bits)] = (uint16_t)level;
+    };
+    // the edges, as k_closure_edges' lanes run them
+    uint64_t reached = 0;
+    for (uint32_t i = 0; i < n; i++)
+        for (uint32_t w = 0; w < stride; w++) {
+            const uint32_t valid = closure_valid(n, w);
+            uint32_t a = 0;
+            if (valid) {
+                const size_t off = (size_t)i * rw + 2u * w;
+                for (uint32_t v : list) {
+                    const uint32_t* base = spec->matrix + (uint64_t)v * n * rw;
+                    a |= closure_bits(base[off], 2u * w + 1u < rw ? base[off + 1] : 0u);
+                }
+                a &= valid;
+            }
+            A[(size_t)i * stride + w] = R[(size_t)i * stride + w] = F[(size_t)i * stride + w] = a;
+            if (a) live[i] = 1;
+            reached += (uint32_t)__builtin_popcount(a);
+            hops(i, w, a, 1u);
+        }
+    result->n_edges = reached;
+    uint32_t level = reached ? 1u : 0u;
+    // one level per pass, as k_closure_step runs it: only live rows, only non-zero frontier words
+    for (uint64_t fresh = reached; fresh && (!spec->max_hops || level < spec->max_hops);) {
+        fresh = 0;
+        for (uint32_t i = 0; i < n; i++) {
+            uint32_t* fn = &Fn[(size_t)i * stride];
+            live_n[i] = 0;
+            std::fill(acc.begin(), acc.end(), 0u);
+            if (live[i])
+                for (uint32_t c = 0; c < chunks; c++)
+                    for (uint32_t f = F[(size_t)i * stride + c]; f; f &= f - 1u) {
+                        const uint32_t* a = &A[(size_t)(32u * c + (uint32_t)__builtin_ctz(f)) * stride];
+                        for (uint32_t w = 0; w < stride; w++) acc[w] |= a[w];
+                    }
+            for (uint32_t w = 0; w < stride; w++) {
+                uint32_t& r = R[(size_t)i * stride + w];
+                const uint32_t nw = closure_new(acc[w], r);
+                r |= nw, fn[w] = nw;
+                if (nw) live_n[i] = 1;
+                fresh += (uint32_t)__builtin_popcount(nw);
+                hops(i, w, nw, level + 1u);
+            }
+        }
+        reached += fresh;
+        if (fresh) level++;
+        F.swap(Fn), live.swap(live_n);
+    }
+    // as k_closure_pack
+    for (uint32_t i = 0; i < n; i++) {
+        uint32_t cnt = 0;
+        for (uint32_t jw = 0; jw < rw; jw++) {
+            const uint32_t h = (R[(size_t)i * stride + (jw >> 1)] >> (16u * (jw & 1u))) & 0xFFFFu;
+            out_packed[(size_t)i * rw + jw] = closure_expand(h);
+            cnt += (uint32_t)__builtin_popcount(h);
+        }
+        if (out_count) out_count[i] = cnt;
+    }
+    *result = pg_reach_closure_result{level, result->n_edges, reached};
+    return PG_OK;
+    GUARD_END(ctx)
+}
+
+int pg_debug_reach_closure_plan(pg_ctx* ctx, uint32_t n, uint32_t* tile_rows, uint32_t* tile_cols, uint32_t* grid) {
+    if (!ctx || !tile_rows || !tile_cols || !grid) return PG_EINVAL;
+    const ClosurePlan p = closure_plan(n);
+    *tile_rows = p.tile_rows, *tile_cols = p.tile_cols, *grid = p.grid;
+    return PG_OK;
 }
 
 }  // extern "C"

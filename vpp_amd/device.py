@@ -335,6 +335,55 @@ def unpack_changes(changes):
     return c[:, 0].copy(), cell & 0xFFFFF, ((cell >> 28) & 3).astype(np.uint8), (cell >> 30).astype(np.uint8)
 
 
+# ---- reachability closure (include/policygpu.h pg_reach_closure) ----------------------------
+def closure_spec(matrix_ptr, n, n_svc, svc_select=None, max_hops=0):
+    """pg_reach_closure_spec -> (spec, the array it points into: keep it alive for the call)"""
+    sel = None
+    if svc_select is not None:
+        sel = np.ascontiguousarray(np.asarray(svc_select) != 0, dtype=np.uint8)
+        if sel.shape != (n_svc,):
+            raise ValueError("svc_select takes one entry per slice")
+    spec = _capi.pg_reach_closure_spec(matrix_ptr, int(n), int(n_svc), sel.ctypes.data if sel is not None else None,
+                                       int(max_hops))
+    return spec, sel
+
+
+def closure_result(res):
+    return {"levels": res.levels, "n_edges": res.n_edges, "n_reachable": res.n_reachable}
+
+
+def reach_closure(engine, matrix, n, svc_select=None, max_hops=0, hops=False, counts=False, stream=None):
+    """Multi-hop reach over the ALLOW graph of a square reach_matrix result, on the GPU
+    (pg_reach_closure). ``matrix`` is an int32 device tensor [n_svc, n, row_words(n)] taken with one
+    end-point list on both sides; ``svc_select`` (one flag per slice, None = all) says which slices
+    contribute edges; ``max_hops`` 0 = until nothing new is found. -> (packed, hops, counts, result):
+    the closure as an int32 tensor [n, row_words(n)] in the audits' layout (ALLOW = reachable;
+    unpack_closure, or reach_diff over two of them), with ``hops`` the hop counts as an int16 tensor
+    [n, n] (0 = not reachable) else None, with ``counts`` the reachable cells of every row as an int32
+    tensor [n] else None, and {levels, n_edges, n_reachable}. The call never touches the hit
+    counters."""
+    rw = reach_row_words(n)
+    if matrix.dtype != torch.int32 or not matrix.is_contiguous() or matrix.numel() % max(1, n * rw):
+        raise ValueError("a contiguous int32 tensor [n_svc, n, row_words(n)] expected")
+    n_svc = matrix.numel() // max(1, n * rw)
+    packed = torch.empty((n, rw), dtype=torch.int32, device="cuda")
+    hop = torch.empty((n, n), dtype=torch.int16, device="cuda") if hops else None
+    cnt = torch.empty(n, dtype=torch.int32, device="cuda") if counts else None
+    res = _capi.pg_reach_closure_result()
+    if n == 0:  # (an empty tensor has no address to hand over; the call would write nothing)
+        return packed, hop, cnt, closure_result(res)
+    spec, keep = closure_spec(matrix.data_ptr(), n, n_svc, svc_select, max_hops)
+    engine._ck(lib.pg_reach_closure(engine.h, C.byref(spec), packed.data_ptr(), hop.data_ptr() if hops else None,
+                                    cnt.data_ptr() if counts else None, C.byref(res), _stream_ptr(stream)))
+    del keep
+    return packed, hop, cnt, closure_result(res)
+
+
+def unpack_closure(packed, n):
+    """packed closure words (tensor or array [n, row_words(n)]) -> bool [n, n], True = reachable"""
+    return unpack_reach(packed, 1, n, n)[0] == 2   # PG_CONN_ALLOW
+
+
 def unpack(out_u32):
     w = out_u32.astype(np.uint32)
     return (w >> 30).astype(np.int64), (w & 0x3FFFFFFF).astype(np.int64)

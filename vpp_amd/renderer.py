@@ -448,6 +448,88 @@ class Engine:
                for r, j, x, y in zip(row, col, cb, ca)]
         return out, trans
 
+    def debug_reach_closure_host(self, matrix, n, svc_select=None, max_hops=0, hops=True, counts=True):
+        """TESTS ONLY: pg_reach_closure's per-word code run on the host (pg_debug_reach_closure_host)
+        over a numpy array of packed words [n_svc, n, row_words(n)]. -> (packed u32 [n, row_words(n)],
+        hops u16 [n, n] or None, counts u32 [n] or None, {levels, n_edges, n_reachable}); the outputs
+        are pre-filled with 0xFF.."""
+        import numpy as np
+        from . import device as D
+        m = np.ascontiguousarray(matrix, dtype=np.uint32)
+        rw = lib.pg_reach_row_words(n)
+        n_svc = m.size // max(1, n * rw)
+        packed = np.full((n, rw), 0xFFFFFFFF, np.uint32)
+        hop = np.full((n, n), 0xFFFF, np.uint16) if hops else None
+        cnt = np.full(n, 0xFFFFFFFF, np.uint32) if counts else None
+        res = _capi.pg_reach_closure_result()
+        if n == 0:
+            return packed, hop, cnt, D.closure_result(res)
+        p = lambda x: x.ctypes.data_as(C.c_void_p)
+        spec, keep = D.closure_spec(m.ctypes.data, n, n_svc, svc_select, max_hops)
+        self._ck(lib.pg_debug_reach_closure_host(self.h, C.byref(spec), p(packed), p(hop) if hops else None,
+                                                 p(cnt) if counts else None, C.byref(res)))
+        del keep
+        return packed, hop, cnt, D.closure_result(res)
+
+    def debug_reach_closure_plan(self, n):
+        """TESTS ONLY: how one level of pg_reach_closure over n end points is cut
+        (pg_debug_reach_closure_plan) -> {tile_rows, tile_cols, grid}"""
+        r, c, g = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        self._ck(lib.pg_debug_reach_closure_plan(self.h, int(n), C.byref(r), C.byref(c), C.byref(g)))
+        return {"tile_rows": r.value, "tile_cols": c.value, "grid": g.value}
+
+    def _closure(self, ips, services, max_hops, host, hops):
+        """one pg_reach_matrix over ips x ips and one closure of all its slices -> (packed, hops,
+        result), device tensors or with ``host`` numpy arrays"""
+        from . import device as D
+        n = len(ips)
+        if host:
+            m = self.debug_reach_matrix_host(ips, ips, services, words=False)
+            packed, hop, _, res = self.debug_reach_closure_host(m, n, None, max_hops, hops=hops, counts=False)
+        else:
+            m = D.reach_matrix(self, ips, ips, services)
+            packed, hop, _, res = D.reach_closure(self, m, n, None, max_hops, hops=hops)
+        return packed, hop, res
+
+    def reachability_closure(self, pods, services, max_hops=0, host=False):
+        """Lateral movement: which pods a pod gets to by hopping through the pods it reaches on any of
+        ``services``, and in how many hops, by one pg_reach_matrix over pods x pods and one
+        pg_reach_closure. -> (reach bool [n, n], hops uint16 [n, n] (0 = not reachable), levels) with
+        the pods as given; ``max_hops`` 0 = no bound. Pods and services as in reachability. ``host``:
+        TESTS ONLY, the host twins instead of the GPU."""
+        import numpy as np
+        from . import device as D
+        ips = self._pod_ips(pods)
+        n = len(ips)
+        if n == 0 or not services:
+            return np.zeros((n, n), bool), np.zeros((n, n), np.uint16), 0
+        packed, hop, res = self._closure(ips, services, max_hops, host, True)
+        if not host:
+            hop = hop.cpu().numpy().view(np.uint16)
+        return D.unpack_closure(packed, n), hop, res["levels"]
+
+    def reachability_closure_diff(self, baseline, pods, services, transitions=_capi.DIFF_OPENED, max_hops=0, host=False):
+        """What a policy change opened (or closed) transitively: the (src pod, dst pod) whose cell of
+        the closure under this engine differs from that under ``baseline`` (another Engine on the same
+        device), by two pg_reach_matrix calls, two pg_reach_closure calls and one pg_reach_diff over
+        the closures. -> [(src pod, dst pod, before, after), ...] in (src, dst) order with the pods as
+        given; before / after are ConnActions, ALLOW = reachable and DENY_SYN = not. ``host``: TESTS
+        ONLY, the host twins."""
+        from . import device as D
+        ips = self._pod_ips(pods)
+        n = len(ips)
+        if n == 0 or not services:
+            return []
+        b, _, _ = baseline._closure(ips, services, max_hops, host, False)
+        a, _, _ = self._closure(ips, services, max_hops, host, False)
+        if host:
+            k, changes, _, _ = self.debug_reach_diff_host(b, a, n, transitions, row_changes=False)
+            changes = changes[:k]
+        else:
+            _, changes, _, _ = D.reach_diff(self, b, a, n, transitions)
+        row, col, cb, ca = D.unpack_changes(changes)
+        return [(pods[int(r)], pods[int(j)], int(x), int(y)) for r, j, x, y in zip(row, col, cb, ca)]
+
     def debug_walk_stats(self, table_id, src, dst, dport, proto):
         """MEASUREMENT: per tuple, the loads a SINGLE launch on table_id makes of the table's
         structure (pg_debug_walk_stats) -> (lds_reads u32[n], mem_reads u32[n], launch STAGE)"""
