@@ -291,6 +291,11 @@ int pg_debug_walk_stats(pg_ctx* ctx, int table_id, const pg_tuple_soa* tuples, u
  * may be null. Does not touch the device. */
 int pg_debug_launch_plan(pg_ctx* ctx, int table_id, int counters, int* stage_code, uint32_t* stage_words,
                          uint32_t* hist_cells);
+/* TESTS ONLY: the geometry of the last classify kernel the calling thread launched (pg_classify):
+ * *block = threads per workgroup, *grid = workgroups launched, *resident = the workgroups the
+ * device holds at once under the launch knobs (the most a grid takes; a launch of more groups
+ * than resident * block strides over them). Zeros before the thread's first launch. */
+int pg_debug_last_launch(int* block, int* grid, int* resident);
 /* TESTS ONLY -- never on the classify path: the launch a PERPOD / CONN pg_classify makes of the
  * compiled table set under the context's launch knobs, with hit counters (counters != 0) or
  * without, from the one function the launch itself dispatches on (device.hpp node_launch_plan).

@@ -245,6 +245,7 @@ _SIGS = {
                                       C.POINTER(C.c_uint32), C.POINTER(C.c_int)]),
     "pg_debug_launch_plan": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_uint32),
                                        C.POINTER(C.c_uint32)]),
+    "pg_debug_last_launch": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "pg_debug_node_launch_plan": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(pg_node_launch_plan)]),
     "pg_stream_probe": (C.c_int, [_P, C.c_int, C.POINTER(pg_tuple_soa), C.c_uint64, _P, _P]),
     "pg_counters_device": (_P, [_P]),

@@ -654,6 +654,10 @@ void host_q(const DevTableSet& T, bool node, int table_id, const pg_tuple_soa* t
         if ((tab.fsk & kFlagCandI) && (tab.fsk & kFlagDstFree)) {  // the kernels' STAGE 6 walk
             const DevLoader b{T.blobs + tab.blob_off};
             classify_candi_q<true, Q>(T, b, b, tab, s, dp, pr, h, o);
+        } else if (tab.fsk & kFlagFD) {  // the kernels' STAGE 4 / 5 group code, the remainder one tuple at a time
+            const DevLoader b{T.blobs + tab.blob_off};
+            if constexpr (Q == 4) classify_fd_group<true, PG_QSINGLE_FD>(T, b, b, tab, s, dp, pr, h, o);
+            else classify_fd_q<true, Q>(T, b, b, tab, s, dp, pr, h, o);
         } else {
             classify_q<0, true, Q, PRED>(T, T.blobs, tab, s, d, sp, dp, pr, h, o);
         }
@@ -733,6 +737,12 @@ int pg_debug_set_snapshot(pg_ctx* ctx, int which, const uint64_t* counters, size
     s.layout = E.layout;
     return PG_OK;
     GUARD_END(ctx)
+}
+
+int pg_debug_last_launch(int* block, int* grid, int* resident) {
+    if (!block || !grid || !resident) return PG_EINVAL;
+    dev_last_launch(block, grid, resident);
+    return PG_OK;
 }
 
 int pg_debug_stream_slots(const uint64_t* streams, size_t n, uint32_t* slot_out, uint32_t* seq_out) {

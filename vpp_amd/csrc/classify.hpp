@@ -31,6 +31,11 @@ namespace pg {
 #ifndef PG_FD_SKIP  // FD walks over a blob in HBM: no re-read of a finished lane's self word
 #define PG_FD_SKIP 1
 #endif
+// SINGLE over an LDS-staged FD table (device.hip STAGE 4): tuples of a group walked in lockstep
+// (classify_fd_group's QC; here because pg_debug_classify_host runs the same group code)
+#ifndef PG_QSINGLE_FD
+#define PG_QSINGLE_FD 1
+#endif
 #ifndef PG_MUL24  // node cross-entry index products as 24-bit multiplies
 #define PG_MUL24 1
 #endif
@@ -558,6 +563,49 @@ PG_HD void classify_fd_q(const DevTableSet& T, const LP& prefix, const LB& blob,
     if (COUNT) {
         PG_UNROLL
         for (int j = 0; j < Q; j++) h.inc(out[j] & kSlotMask);
+    }
+}
+
+// One group of P tuples of a lane over an FD table: the body of the kernels' STAGE 4 / 5 group
+// loop, and what pg_debug_classify_host runs over full groups. The walks go QC tuples at a time
+// in lockstep (fd_walk<QC>: a level's reads of the QC src and QC key walks issued together, one
+// wait per level). The ANY-protocol test is made once over the group's keys, and the linear scan
+// of those packets is reached by one call site after every walk -- a lane's pending tuples one
+// per pass, picked by selects, so the registers are never indexed -- and no call stands between
+// the tuples' read chains.
+template <bool COUNT, int QC, int P, class LP, class LB>
+PG_HD void classify_fd_group(const DevTableSet& T, const LP& prefix, const LB& blob, const DevTable& tab0,
+                             const uint32_t (&s)[P], const uint32_t (&dp)[P], const uint32_t (&pr)[P], const Hist& h,
+                             uint32_t (&out)[P]) {
+    static_assert(P % QC == 0 && P <= 32, "a group is whole chunks, its pending tuples one bit each");
+    uint32_t key[P], pend = 0;
+    PG_UNROLL
+    for (int j = 0; j < P; j++) key[j] = pkt_key(pr[j], dp[j]), pend |= (key[j] >= kWalkKeyLimit ? 1u : 0u) << j;
+    PG_UNROLL
+    for (int c = 0; c < P; c += QC) {
+        uint32_t cs[QC], ck[QC], co[QC];
+        PG_UNROLL
+        for (int j = 0; j < QC; j++) cs[j] = s[c + j], ck[j] = key[c + j];
+        fd_walk<PG_FD_SKIP && !std::is_same<LB, LdsLoader>::value>(prefix, blob, tab0.fsk, tab0.kroot, tab0.xoff, tab0.nkc,
+                                                                   cs, ck, co);
+        PG_UNROLL
+        for (int j = 0; j < QC; j++) out[c + j] = co[j];
+    }
+    while (pend) {  // no rule of an FD table tests dst (engine.cpp): any dst will do
+        const uint32_t j = (uint32_t)__builtin_ctz(pend);
+        uint32_t sj = s[0], kj = key[0];
+        PG_UNROLL
+        for (int i = 1; i < P; i++)
+            if (j == (uint32_t)i) sj = s[i], kj = key[i];
+        const uint32_t w = eval_linear(T.rules, tab0.rule_base, tab0.n_rules, tab0.dflt, sj, 0u, kj);
+        PG_UNROLL
+        for (int i = 0; i < P; i++)
+            if (j == (uint32_t)i) out[i] = w;
+        pend &= pend - 1u;
+    }
+    if (COUNT) {
+        PG_UNROLL
+        for (int j = 0; j < P; j++) h.inc(out[j] & kSlotMask);
     }
 }
 

@@ -441,15 +441,41 @@ bool dev_candi_lean() { return PG_CANDI_LEAN != 0; }
 #ifndef PG_QCONN_COUNT  // CONN with hit counters (A/B on MI355X, config 5: 2 = +9 % over 1, 4 = -6 % in
 #define PG_QCONN_COUNT 1  // round 1; after the fixed-depth node walks 1 = +3.5 % over 2, tune1)
 #endif
-#ifndef PG_QSINGLE_FD  // SINGLE over an LDS-staged FD table (STAGE 4)
-#define PG_QSINGLE_FD 1
+// (PG_QSINGLE_FD, SINGLE over an LDS-staged FD table without counters at 512 threads: classify.hpp)
+#ifndef PG_QSINGLE_FD_OTHER  // ... with counters, or at 1024 threads (blobs above a third of LDS)
+#define PG_QSINGLE_FD_OTHER 1
 #endif
 #ifndef PG_QSINGLE_FDG  // SINGLE over an FD table read from HBM, its prefix staged (STAGE 5): 4 (A/B on
                         // MI355X with the finished-lane skip: 30k / 100k / config 7 +2 / +1.2 / +1.2 % over 2)
 #define PG_QSINGLE_FDG 4
 #endif
-#ifndef PG_PREFETCH_FD  // STAGE 4 / 5: stream prefetch of the next group (see PG_PREFETCH)
-#define PG_PREFETCH_FD 0
+// The FD-in-LDS launch without counters at 512 threads (config 2; DESIGN.md Appendix A round 7, A/B
+// on MI355X against the parent's 521 / 533 Gpps warmed and 543 / 527 in the driver's window, two
+// rounds each): the next group's stream loads issued at the top of the iteration (1), the first
+// group's before the staging copy's, and a group through classify_fd_group: 543 / 543 and 557 /
+// 561. Without the early first loads 516 / 525 and 531 / 532 (with the batched copy); two groups
+// ahead (PG_PF_DEPTH 2) 526 / 527; the loads after the group's store (3) 516 / 516; three or
+// four workgroups per CU with the prefetch 488-495 (two: 536).
+#ifndef PG_PREFETCH_FD
+#define PG_PREFETCH_FD 1
+#endif
+#ifndef PG_PREFETCH_FD_OTHER  // ... STAGE 4 with counters or at 1024 threads, and STAGE 5
+#define PG_PREFETCH_FD_OTHER 0
+#endif
+#ifndef PG_FD_GROUP  // a group through classify_fd_group (classify.hpp), else chunk by chunk
+#define PG_FD_GROUP 1
+#endif
+#ifndef PG_FD_GROUP_OTHER  // ... STAGE 4 with counters or at 1024 threads, and STAGE 5
+#define PG_FD_GROUP_OTHER 0
+#endif
+#ifndef PG_FD_EARLY_LOAD  // with stream prefetch: the first group's stream loads issued before the staging copy's
+#define PG_FD_EARLY_LOAD 1
+#endif
+// the staging copy's 16-byte loads in batches of four independent registers: off -- two waits
+// instead of six, but every workgroup's burst of loads at the same blob measured slower (config 2
+// with the prefetch and the early loads: 522 / 537 and 540 / 541 Gpps against 543 / 543 and 557 / 561)
+#ifndef PG_STAGE_BATCH
+#define PG_STAGE_BATCH 0
 #endif
 #ifndef PG_PF_DEPTH  // launches with stream prefetch: groups loaded ahead (1 or 2)
 #define PG_PF_DEPTH 1
@@ -558,6 +584,30 @@ __device__ __forceinline__ void st_words(const Words<NW>& v, uint32_t* p) {
 #pragma unroll
     for (int k = 0; k < NW / 4; k++)
         stream_store(v4u{v.w[4 * k], v.w[4 * k + 1], v.w[4 * k + 2], v.w[4 * k + 3]}, reinterpret_cast<v4u*>(p) + k);
+}
+// The staging copy: nv 16-byte words of an image from global memory g to LDS s by the workgroup's
+// BS threads. Each thread issues four independent loads, then writes the four to LDS -- one wait
+// per batch of 4 BS words, not one full memory latency per word -- and the words left over
+// (fewer than 4 BS) go as one more batch of up to three loads per thread. An image of 64 KiB
+// takes two waits at 512 threads (PG_STAGE_BATCH 0: the plain word-at-a-time loop, for A/B).
+template <int BS>
+__device__ __forceinline__ void stage_copy(uint4* __restrict__ s, const uint4* __restrict__ g, uint32_t nv) {
+#if PG_STAGE_BATCH
+    uint32_t i = threadIdx.x;
+    for (; i + 3u * BS < nv; i += 4u * BS) {
+        const uint4 a = g[i], b = g[i + BS], c = g[i + 2u * BS], d = g[i + 3u * BS];
+        s[i] = a, s[i + BS] = b, s[i + 2u * BS] = c, s[i + 3u * BS] = d;
+    }
+    uint4 r[3];
+#pragma unroll
+    for (uint32_t k = 0; k < 3u; k++)
+        if (i + k * BS < nv) r[k] = g[i + k * BS];
+#pragma unroll
+    for (uint32_t k = 0; k < 3u; k++)
+        if (i + k * BS < nv) s[i + k * BS] = r[k];
+#else
+    for (uint32_t i = threadIdx.x; i < nv; i += BS) s[i] = g[i];
+#endif
 }
 #ifndef PG_NODE_WPE  // node kernels: minimum waves per SIMD the register allocation must allow (1 = any)
 #define PG_NODE_WPE 1
@@ -761,15 +811,69 @@ void k_classify(DevTableSet T, int32_t t, const uint32_t* __restrict__ src,
     using ImgLoader = std::conditional_t<NODE && STAGE != 0, LdsLoader, DevLoader>;
     ImgLoader img{};
     if constexpr (NODE && STAGE == 0) img = DevLoader{T.node.img};
-    if (NODE && STAGE) {
-        const uint4* g = reinterpret_cast<const uint4*>(T.node.img);
-        for (uint32_t i = threadIdx.x; i < stage_words / 4u; i += BS) reinterpret_cast<uint4*>(smem)[i] = g[i];
-    }
+    // group indices and stream offsets in 32 bits (PG_IDX32: the launcher keeps a launch below
+    // kMaxLaunchTuples, so every byte offset of a stream fits 32 bits): a load is then the SGPR base
+    // plus a 32-bit VGPR offset, with no 64-bit address arithmetic per stream and group
+    using Idx = std::conditional_t<PG_IDX32 != 0, uint32_t, uint64_t>;
+    const Idx stride = (Idx)gridDim.x * BS;
+    const Idx first = (Idx)blockIdx.x * BS + threadIdx.x;
+    // full groups of P tuples per lane (P = tuples_per_lane): SoA fields read with 16/8/4-byte loads per
+    // lane (coalesced, non-temporal); prefetch 1/2: the next group's loads are in flight
+    // while this group is classified
+    constexpr int P = tuples_per_lane<MODE>();
+    static_assert(P % 4 == 0, "a group's protocol bytes are loaded as whole words (PG_TPL, PG_TPL_CONN)");
+    const Idx nfull = VEC ? (Idx)(n / P) : 0;
+    // element i of a stream, its byte offset computed in Idx
+    auto el = [](auto* base, Idx i) {
+        using E = std::remove_pointer_t<decltype(base)>;
+        using C = std::conditional_t<std::is_const<E>::value, const char, char>;
+        return reinterpret_cast<decltype(base)>(reinterpret_cast<C*>(base) + (Idx)(i * (Idx)sizeof(E)));
+    };
+    struct Group {
+        Words<P> s, d;
+        Words<P / 2> dp, sp;
+        Words<P / 4> pr;
+    };
+    // STAGE 4 / 5 (SINGLE over an FD table): no rule tests dst, so the dst stream is not read
+    constexpr bool FD = MODE == 0 && (STAGE == 4 || STAGE == 5);
+    constexpr bool NEED_DST = !FD && !NODST;
+    auto load = [&](Idx q) {
+        Group x;
+        const Idx i0 = q * P;
+        x.s = ld_words<P>(el(src, i0));
+        if (NEED_DST) x.d = ld_words<P>(el(dst, i0));
+        else x.d = Words<P>{};
+        x.dp = ld_words<P / 2>(reinterpret_cast<const uint32_t*>(el(dport, i0)));
+        x.pr = ld_words<P / 4>(reinterpret_cast<const uint32_t*>(el(proto, i0)));
+        if (MODE == 2) x.sp = ld_words<P / 2>(reinterpret_cast<const uint32_t*>(el(sport, i0)));
+        else x.sp = Words<P / 2>{};
+        return x;
+    };
+    Idx q = first;
+    Group cur;
+    // default: SINGLE over an LDS-staged blob none, SINGLE over a blob in HBM (STAGE 0 / 2) and
+    // the node modes the next group at the top of the iteration (A/B on MI355X, config 4 with
+    // four tuples per chunk: 172.9 vs 169.3 Gpps)
+    // the FD-in-LDS launch bench.py measures (config 2): no counters, 512 threads; the counted and
+    // the 1024-thread builds and STAGE 5 have knobs of their own (each by its own A/B)
+    constexpr bool FD_MAIN = FD && STAGE == 4 && !COUNT && BS == 512;
+    constexpr int PF0 = FD ? (FD_MAIN ? PG_PREFETCH_FD : PG_PREFETCH_FD_OTHER)
+                          : (PG_PREFETCH >= 0 ? PG_PREFETCH
+                                              : ((MODE == 0 && STAGE != 0 && STAGE != 2 && STAGE != 6) ||
+                                                 node_wide<MODE, COUNT, NODE, STAGE_>()
+                                                     ? 0 : 1));
+    constexpr int PF = (!NODE && PF0 == 2) ? 1 : PF0;  // (only node kernels have the gather hook)
+    // STAGE 4 / 5 with stream prefetch: the first group's stream loads go out before the staging
+    // copy's (they need the kernel's arguments only), so the tuple streams are moving while the
+    // blob is copied and the barrier waited for. (A loop without prefetch loads at the top of every
+    // iteration: a first group loaded here would cost it a test per iteration.)
+    constexpr bool EARLY = FD && PF != 0 && PG_FD_EARLY_LOAD;
+    if (EARLY && q < nfull) cur = load(q);
+    if (NODE && STAGE) stage_copy<BS>(reinterpret_cast<uint4*>(smem), reinterpret_cast<const uint4*>(T.node.img), stage_words / 4u);
     if (MODE == 0) {
         tab0 = load_tab(T.tabs, t);
         if (STAGE) {
-            const uint4* g = reinterpret_cast<const uint4*>(T.blobs + tab0.blob_off);
-            for (uint32_t i = threadIdx.x; i < stage_words / 4u; i += BS) reinterpret_cast<uint4*>(smem)[i] = g[i];
+            stage_copy<BS>(reinterpret_cast<uint4*>(smem), reinterpret_cast<const uint4*>(T.blobs + tab0.blob_off), stage_words / 4u);
             if (STAGE == 1 || STAGE == 4) {  // (STAGE 5: the prefix in LDS, the rest read from HBM)
                 blobs = smem;
                 tab0.blob_off = 0;
@@ -832,56 +936,7 @@ void k_classify(DevTableSet T, int32_t t, const uint32_t* __restrict__ src,
         }
     }
     if (STAGE || COUNT) __syncthreads();
-    // group indices and stream offsets in 32 bits (PG_IDX32: the launcher keeps a launch below
-    // kMaxLaunchTuples, so every byte offset of a stream fits 32 bits): a load is then the SGPR base
-    // plus a 32-bit VGPR offset, with no 64-bit address arithmetic per stream and group
-    using Idx = std::conditional_t<PG_IDX32 != 0, uint32_t, uint64_t>;
-    const Idx stride = (Idx)gridDim.x * BS;
-    const Idx first = (Idx)blockIdx.x * BS + threadIdx.x;
-    // full groups of P tuples per lane (P = tuples_per_lane): SoA fields read with 16/8/4-byte loads per
-    // lane (coalesced, non-temporal); prefetch 1/2: the next group's loads are in flight
-    // while this group is classified
-    constexpr int P = tuples_per_lane<MODE>();
-    static_assert(P % 4 == 0, "a group's protocol bytes are loaded as whole words (PG_TPL, PG_TPL_CONN)");
-    const Idx nfull = VEC ? (Idx)(n / P) : 0;
-    // element i of a stream, its byte offset computed in Idx
-    auto el = [](auto* base, Idx i) {
-        using E = std::remove_pointer_t<decltype(base)>;
-        using C = std::conditional_t<std::is_const<E>::value, const char, char>;
-        return reinterpret_cast<decltype(base)>(reinterpret_cast<C*>(base) + (Idx)(i * (Idx)sizeof(E)));
-    };
-    struct Group {
-        Words<P> s, d;
-        Words<P / 2> dp, sp;
-        Words<P / 4> pr;
-    };
-    // STAGE 4 / 5 (SINGLE over an FD table): no rule tests dst, so the dst stream is not read
-    constexpr bool FD = MODE == 0 && (STAGE == 4 || STAGE == 5);
-    constexpr bool NEED_DST = !FD && !NODST;
     const uint32_t* fd_blob = FD ? (STAGE == 4 ? smem : T.blobs + tab0.blob_off) : nullptr;
-    auto load = [&](Idx q) {
-        Group x;
-        const Idx i0 = q * P;
-        x.s = ld_words<P>(el(src, i0));
-        if (NEED_DST) x.d = ld_words<P>(el(dst, i0));
-        else x.d = Words<P>{};
-        x.dp = ld_words<P / 2>(reinterpret_cast<const uint32_t*>(el(dport, i0)));
-        x.pr = ld_words<P / 4>(reinterpret_cast<const uint32_t*>(el(proto, i0)));
-        if (MODE == 2) x.sp = ld_words<P / 2>(reinterpret_cast<const uint32_t*>(el(sport, i0)));
-        else x.sp = Words<P / 2>{};
-        return x;
-    };
-    Idx q = first;
-    Group cur;
-    // default: SINGLE over an LDS-staged blob none, SINGLE over a blob in HBM (STAGE 0 / 2) and
-    // the node modes the next group at the top of the iteration (A/B on MI355X, config 4 with
-    // four tuples per chunk: 172.9 vs 169.3 Gpps)
-    constexpr int PF0 = FD ? PG_PREFETCH_FD
-                          : (PG_PREFETCH >= 0 ? PG_PREFETCH
-                                              : ((MODE == 0 && STAGE != 0 && STAGE != 2 && STAGE != 6) ||
-                                                 node_wide<MODE, COUNT, NODE, STAGE_>()
-                                                     ? 0 : 1));
-    constexpr int PF = (!NODE && PF0 == 2) ? 1 : PF0;  // (only node kernels have the gather hook)
     // PD = 2 (PG_PF_DEPTH): the loads run two groups ahead (group q + 2 * stride is
     // loaded while group q is classified). PF 3: the loads are issued after the group's
     // classification (its gathers waited for) and verdict store. Vector-memory
@@ -916,12 +971,17 @@ void k_classify(DevTableSet T, int32_t t, const uint32_t* __restrict__ src,
         // lane, more waves per SIMD)
         constexpr int QC = MODE == 2 ? (COUNT ? PG_QCONN_COUNT : PG_QCONN)
                                      : (MODE == 1 ? (FULLH ? PG_QPOD_FULLH : PG_QPOD)
-                                                  : (FD ? (STAGE == 4 ? PG_QSINGLE_FD : PG_QSINGLE_FDG)
+                                                  : (FD ? (FD_MAIN      ? PG_QSINGLE_FD
+                                                           : STAGE == 4 ? PG_QSINGLE_FD_OTHER
+                                                                        : PG_QSINGLE_FDG)
                                                         : (STAGE == 1   ? PG_QSINGLE_LDS
                                                            : STAGE == 6 ? (COUNT ? PG_QSINGLE : PG_QCANDI)
                                                                         : PG_QSINGLE)));
         if constexpr (MODE == 0 && STAGE == 6 && PG_CANDI_COMPACT) {
             classify_candi_group<COUNT, P>(T, tab0, cscr, sv, dpv, prv, h, o);
+        } else if constexpr (FD && (FD_MAIN ? PG_FD_GROUP : PG_FD_GROUP_OTHER)) {  // the group as a whole (classify.hpp: one ANY test, one linear-scan call site)
+            if constexpr (STAGE == 4) classify_fd_group<COUNT, QC>(T, LdsLoader{}, LdsLoader{}, tab0, sv, dpv, prv, h, o);
+            else classify_fd_group<COUNT, QC>(T, LdsLoader{}, DevLoader{fd_blob}, tab0, sv, dpv, prv, h, o);
         } else
 #pragma unroll
         for (int c = 0; c < P; c += QC) {
@@ -929,7 +989,7 @@ void k_classify(DevTableSet T, int32_t t, const uint32_t* __restrict__ src,
 #pragma unroll
             for (int j = 0; j < QC; j++)
                 cs[j] = sv[c + j], cd[j] = dv[c + j], csp[j] = spv[c + j], cdp[j] = dpv[c + j], cpr[j] = prv[c + j];
-            if constexpr (FD) {
+            if constexpr (FD) {  // (PG_FD_GROUP 0: chunk by chunk, each with its own ANY test and scan)
                 if constexpr (STAGE == 4) classify_fd_q<COUNT, QC>(T, LdsLoader{}, LdsLoader{}, tab0, cs, cdp, cpr, h, co);
                 else classify_fd_q<COUNT, QC>(T, LdsLoader{}, DevLoader{fd_blob}, tab0, cs, cdp, cpr, h, co);
             } else if constexpr (MODE == 0 && STAGE == 6) {
@@ -952,7 +1012,7 @@ void k_classify(DevTableSet T, int32_t t, const uint32_t* __restrict__ src,
         st_words<P>(ow, el(out, qq * P));
     };
     Group ahead{};
-    if (PF && q < nfull) cur = load(q);
+    if (PF && !EARLY && q < nfull) cur = load(q);  // (EARLY: loaded before the staging copy)
     if (PD == 2 && q + stride < nfull) ahead = load(q + stride);
     while (q < nfull) {
         const Idx qn = q + stride, qa = PD == 2 ? qn + stride : qn;  // qa: the group loaded now
@@ -1181,10 +1241,18 @@ static int grid_for(uint64_t items, uint32_t blocks_per_cu = 0) {
 }
 
 // grid_resident (hiputil.hpp) of a classify kernel, traced under PG_DEBUG_LAUNCH
+// (the geometry of the calling thread's last classify launch: dev_last_launch, tests only)
+// resident: the workgroups the device holds at once, the most a launch's grid takes
+static thread_local int t_last_block = 0, t_last_grid = 0, t_last_resident = 0;
+void dev_last_launch(int* block, int* grid, int* resident) {
+    *block = t_last_block, *grid = t_last_grid, *resident = t_last_resident;
+}
 template <class K>
 static int grid_classify(K kernel, int bs, size_t lds, uint64_t items, uint32_t blocks_per_cu) {
     int occ = 0;
     const int grid = grid_resident(kernel, bs, lds, items, blocks_per_cu, &occ);
+    t_last_block = bs, t_last_grid = grid;
+    t_last_resident = num_cus() * (blocks_per_cu ? std::min<int>(occ, (int)blocks_per_cu) : occ);
     static const bool dbg = std::getenv("PG_DEBUG_LAUNCH") != nullptr;  // measurement aid: launch geometry
     if (dbg) std::fprintf(stderr, "pg launch: block %d, LDS %zu B, occupancy %d blocks/CU, grid %d\n", bs, lds, occ, grid);
     return grid;

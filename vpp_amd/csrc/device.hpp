@@ -465,6 +465,9 @@ int dev_counters_remap(unsigned long long* dst, const unsigned long long* src, c
 // the launch-mark word of `stream` for table set b and the next launch number at it (StreamSlots)
 uint32_t* dev_any_mark(DeviceBuffers* b, void* stream, uint32_t* seq, std::string* err);
 int dev_wait_uses(DeviceBuffers* b, std::string* err);
+// tests only: workgroup size and grid of the calling thread's last classify launch, and the
+// workgroups resident at once under its launch knobs
+void dev_last_launch(int* block, int* grid, int* resident);
 // RCCL communicators (opaque ncclComm_t), librccl opened on first use
 int dev_comm_unique_id(uint8_t* id /* 128 B */, std::string* err);
 void* dev_comm_init_rank(int nranks, const uint8_t* id, int rank, std::string* err);

@@ -91,6 +91,16 @@ def classify(engine, mode, table_id, batch, out, counters=None, stream=None, off
                                _stream_ptr(stream)))
 
 
+def last_launch():
+    """TESTS ONLY: {block, grid, resident} of this thread's last classify kernel launch
+    (pg_debug_last_launch): threads per workgroup, workgroups launched, and the workgroups the
+    device holds at once under the launch knobs"""
+    b, g, r = C.c_int(), C.c_int(), C.c_int()
+    if lib.pg_debug_last_launch(C.byref(b), C.byref(g), C.byref(r)) != 0:
+        raise RuntimeError("pg_debug_last_launch")
+    return {"block": b.value, "grid": g.value, "resident": r.value}
+
+
 def classify_linear(engine, table_id, batch, out, stream=None):
     soa = batch.soa()
     engine._ck(lib.pg_classify_linear(engine.h, table_id, C.byref(soa), batch.n, out.data_ptr(),
