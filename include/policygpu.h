@@ -655,6 +655,59 @@ int pg_debug_reach_closure_host(pg_ctx* ctx, const pg_reach_closure_spec* spec, 
  * owns and the workgroups of a level. Launches nothing. */
 int pg_debug_reach_closure_plan(pg_ctx* ctx, uint32_t n, uint32_t* tile_rows, uint32_t* tile_cols, uint32_t* grid);
 
+/* ---- reachability groups: a matrix summed into (src group, dst group) pairs, on the device ---
+ * "Can anything in dev reach anything in prod on 5432? Is frontend -> api fully open or only
+ * partly?" The input is a pg_reach_matrix out_packed, which stays on the device in its 2 bits per
+ * cell; every src and every dst end point is given a group (a namespace, a deployment, a label
+ * set) or PG_GROUP_SKIP.
+ *   out_counts  device, required, n_svc * n_src_groups * n_dst_groups * 4 uint64_t: entry
+ *               ((v * n_src_groups + gs) * n_dst_groups + gd) * 4 + c is the number of cells (v, i, j)
+ *               with src_group[i] == gs, dst_group[j] == gd and ConnAction c. Every entry is written,
+ *               zeros included (the call clears the array on the stream first). Integer sums: exact,
+ *               and the same on every run.
+ *   out_packed  device, optional: the PG_GROUPS_* status of every (v, gs, gd) in the audits' layout,
+ *               n_svc * n_src_groups rows of pg_reach_row_words(n_dst_groups) words, cell gd in bits
+ *               [2 * (gd & 15), 2 * (gd & 15) + 1] of word gd / 16, the padding bits of a row's last
+ *               word zero. A valid before / after of pg_reach_diff with n_cols = n_dst_groups: the
+ *               diff of two summaries lists the group pairs whose status a policy change moved.
+ *               PG_GROUPS_ALL equals PG_CONN_ALLOW, so pg_reach_closure over a square summary
+ *               follows the fully open pairs.
+ * Any assignment of ids is allowed: not contiguous, not sorted, groups without members, every end
+ * point its own group. A pod that belongs to two groups is listed twice in the end-point list that
+ * pg_reach_matrix was given. The padding bits of the input rows are masked, never trusted. Like
+ * pg_reach_diff the call reads no table and triggers no compile, and it never touches the hit
+ * counters or their snapshots; ctx only names the device and its launch knobs. It copies the two
+ * host arrays in, enqueues in order on hip_stream and synchronises that stream before it returns.
+ * n_svc, n_src or n_dst zero: PG_OK, out_counts cleared and out_packed all PG_GROUPS_EMPTY (the
+ * matrix may then be null); with a group count of zero as well, nothing is written. PG_EINVAL
+ * (pg_last_error says which argument, and for a bad id which index): a null spec, matrix or
+ * out_counts; a null src_group / dst_group where that side is not empty; a side above 2^20; n_svc
+ * above 4096; a group count of 0 or above 4096; n_svc * n_src_groups * n_dst_groups >= 2^30; a group
+ * id that is neither below its count nor PG_GROUP_SKIP. PG_ENOMEM: the scratch allocation (the
+ * sorted rows and the ids) failed. */
+#define PG_GROUP_SKIP 0xFFFFFFFFu   /* an end point that belongs to no group: its row / column is counted nowhere */
+enum { PG_GROUPS_NONE = 0,   /* the pair has cells, none of them ALLOW            */
+       PG_GROUPS_SOME = 1,   /* some cells ALLOW, some not                         */
+       PG_GROUPS_ALL = 2,    /* every cell ALLOW (same value as PG_CONN_ALLOW)     */
+       PG_GROUPS_EMPTY = 3 };/* no cell: one of the two groups has no member       */
+typedef struct pg_reach_groups_spec {
+    const uint32_t* matrix;      /* device: a pg_reach_matrix out_packed, n_svc * n_src rows of pg_reach_row_words(n_dst) words */
+    uint32_t n_svc, n_src, n_dst;
+    const uint32_t* src_group;   /* host, n_src entries: < n_src_groups, or PG_GROUP_SKIP */
+    const uint32_t* dst_group;   /* host, n_dst entries: < n_dst_groups, or PG_GROUP_SKIP */
+    uint32_t n_src_groups, n_dst_groups;   /* 1 .. 4096 each */
+} pg_reach_groups_spec;
+int pg_reach_groups(pg_ctx* ctx, const pg_reach_groups_spec* spec, uint64_t* out_counts, uint32_t* out_packed,
+                    void* hip_stream);
+/* TESTS ONLY -- never on the audit path: pg_reach_groups's per-word code (groups.hpp, the functions
+ * the kernels call) on the host, work item by work item; matrix, out_counts and out_packed are host
+ * arrays. Does not touch the device. */
+int pg_debug_reach_groups_host(pg_ctx* ctx, const pg_reach_groups_spec* spec, uint64_t* out_counts, uint32_t* out_packed);
+/* TESTS ONLY: how a pg_reach_groups over rows of n_dst cells is cut, from the one function the
+ * launch itself uses (groups.hpp groups_plan): the column words of a work item's tile and the most
+ * rows of one src group it walks between two flushes. Launches nothing. */
+int pg_debug_reach_groups_plan(pg_ctx* ctx, uint32_t n_dst, uint32_t* tile_words, uint32_t* chunk_rows);
+
 /* ---- policy configurator ------------------------------------------
  * configurator.PolicyConfiguratorAPI / Txn (plugins/policy/configurator/configurator_api.go:28-54,
  * configurator_impl.go:104-472): K8s-shaped policies per pod -> ordered ContivRule lists

@@ -22,6 +22,9 @@ PG_OK, PG_ENOENT, PG_EIO, PG_ENOMEM, PG_EINVAL, PG_EFAULT = 0, -2, -5, -12, -22,
 MODE_SINGLE, MODE_PERPOD, MODE_CONN = 0, 1, 2
 # pg_reach_diff transitions: bit 4 * before + after (ConnActions; ALLOW = 2)
 DIFF_ALL, DIFF_OPENED, DIFF_CLOSED = 0xFFFF, 0x4044, 0x0B00
+# pg_reach_groups: an end point in no group, and the status of a (src group, dst group) pair
+GROUP_SKIP = 0xFFFFFFFF
+GROUPS_NONE, GROUPS_SOME, GROUPS_ALL, GROUPS_EMPTY = 0, 1, 2, 3
 ORIENT_INGRESS, ORIENT_EGRESS = 0, 1
 
 
@@ -110,6 +113,12 @@ class pg_reach_closure_spec(C.Structure):
 
 class pg_reach_closure_result(C.Structure):
     _fields_ = [("levels", C.c_uint32), ("n_edges", C.c_uint64), ("n_reachable", C.c_uint64)]
+
+
+class pg_reach_groups_spec(C.Structure):
+    _fields_ = [("matrix", C.c_void_p), ("n_svc", C.c_uint32), ("n_src", C.c_uint32), ("n_dst", C.c_uint32),
+                ("src_group", C.c_void_p), ("dst_group", C.c_void_p), ("n_src_groups", C.c_uint32),
+                ("n_dst_groups", C.c_uint32)]
 
 
 class pg_pod_id(C.Structure):
@@ -270,6 +279,9 @@ _SIGS = {
                                               C.POINTER(pg_reach_closure_result)]),
     "pg_debug_reach_closure_plan": (C.c_int, [_P, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                               C.POINTER(C.c_uint32)]),
+    "pg_reach_groups": (C.c_int, [_P, C.POINTER(pg_reach_groups_spec), _P, _P, _P]),
+    "pg_debug_reach_groups_host": (C.c_int, [_P, C.POINTER(pg_reach_groups_spec), _P, _P]),
+    "pg_debug_reach_groups_plan": (C.c_int, [_P, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "pg_session_rules_new": (_P, [C.c_char_p]),
     "pg_session_rules_free": (None, [_P]),
     "pg_session_rules_clear": (C.c_int, [_P]),

@@ -1,11 +1,12 @@
 // extern "C" boundary of the reachability audits (include/policygpu.h): the matrix, the port sweep,
-// the diff and the closure, each with the host twin the tests compare its kernels to.
+// the diff, the closure and the groups, each with the host twin the tests compare its kernels to.
 #include <algorithm>
 #include <numeric>
 
 #include "capi_internal.hpp"
 #include "closure.hpp"
 #include "diff.hpp"
+#include "groups.hpp"
 #include "ports.hpp"
 
 using namespace pg;
@@ -484,6 +485,114 @@ int pg_debug_reach_closure_plan(pg_ctx* ctx, uint32_t n, uint32_t* tile_rows, ui
     if (!ctx || !tile_rows || !tile_cols || !grid) return PG_EINVAL;
     const ClosurePlan p = closure_plan(n);
     *tile_rows = p.tile_rows, *tile_cols = p.tile_cols, *grid = p.grid;
+    return PG_OK;
+}
+
+}  // extern "C"
+
+// ---- reachability groups (groups.hpp) ------------------------------------------------------------
+namespace {
+static_assert(PG_GROUP_SKIP == kGroupsSkip && (int)PG_GROUPS_ALL == (int)PG_CONN_ALLOW, "groups.hpp's constants are the header's");
+
+// argument checks shared by pg_reach_groups and its host twin: PG_OK with *nothing set when no
+// output has an entry (no service, or an empty side with a group count of zero)
+int groups_args(pg_ctx* ctx, const pg_reach_groups_spec* spec, const uint64_t* out_counts, bool* nothing) {
+    if (!ctx) return PG_EINVAL;
+    if (!spec || !out_counts) return fail(ctx, PG_EINVAL, "null spec or out_counts");
+    if (spec->n_src > kGroupsMaxSide || spec->n_dst > kGroupsMaxSide) return fail(ctx, PG_EINVAL, "a side longer than 2^20");
+    if (spec->n_svc > kGroupsMaxSvc) return fail(ctx, PG_EINVAL, "more than 4096 services");
+    if (spec->n_src_groups > kGroupsMaxGroups || spec->n_dst_groups > kGroupsMaxGroups)
+        return fail(ctx, PG_EINVAL, "n_src_groups or n_dst_groups above 4096");
+    const bool empty = !spec->n_svc || !spec->n_src || !spec->n_dst;
+    if (!spec->n_src_groups || !spec->n_dst_groups) {
+        if (!empty) return fail(ctx, PG_EINVAL, "n_src_groups or n_dst_groups is 0");
+        *nothing = true;
+        return PG_OK;
+    }
+    if ((uint64_t)spec->n_svc * spec->n_src_groups * spec->n_dst_groups >> 30)
+        return fail(ctx, PG_EINVAL, "n_svc * n_src_groups * n_dst_groups reaches 2^30");
+    if (!spec->matrix && !empty) return fail(ctx, PG_EINVAL, "null matrix");
+    if ((spec->n_src && !spec->src_group) || (spec->n_dst && !spec->dst_group))
+        return fail(ctx, PG_EINVAL, "null src_group or dst_group");
+    auto ids = [&](const char* what, const uint32_t* g, uint32_t n, uint32_t count) {
+        for (uint32_t i = 0; i < n; i++)
+            if (g[i] >= count && g[i] != kGroupsSkip)
+                return fail(ctx, PG_EINVAL, std::string(what) + "[" + std::to_string(i) + "] = " + std::to_string(g[i]) +
+                                                " is neither below its group count nor PG_GROUP_SKIP");
+        return (int)PG_OK;
+    };
+    if (int rc = ids("src_group", spec->src_group, spec->n_src, spec->n_src_groups)) return rc;
+    if (int rc = ids("dst_group", spec->dst_group, spec->n_dst, spec->n_dst_groups)) return rc;
+    *nothing = !spec->n_svc;
+    return PG_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int pg_reach_groups(pg_ctx* ctx, const pg_reach_groups_spec* spec, uint64_t* out_counts, uint32_t* out_packed, void* stream) {
+    GUARD_BEGIN
+    bool nothing = false;
+    if (int rc = groups_args(ctx, spec, out_counts, &nothing)) return rc;
+    if (nothing) return PG_OK;
+    DEVICE_GUARD(ctx);
+    const GroupsPartition part = groups_partition(spec->src_group, spec->n_src, spec->n_src_groups, spec->dst_group,
+                                                  spec->n_dst, groups_plan(spec->n_dst).chunk_rows);
+    const GroupsSpecDev sd{spec->matrix, spec->n_svc, spec->n_src, spec->n_dst, spec->n_src_groups, spec->n_dst_groups, &part};
+    std::string err;
+    const int rc = dev_reach_groups(ctx->eng.tune.blocks_per_cu, sd, out_counts, out_packed, stream, &err);
+    if (rc != 0) return fail(ctx, rc == -2 ? PG_ENOMEM : PG_EIO, err);
+    return PG_OK;
+    GUARD_END(ctx)
+}
+
+int pg_debug_reach_groups_host(pg_ctx* ctx, const pg_reach_groups_spec* spec, uint64_t* out_counts, uint32_t* out_packed) {
+    GUARD_BEGIN
+    bool nothing = false;
+    if (int rc = groups_args(ctx, spec, out_counts, &nothing)) return rc;
+    if (nothing) return PG_OK;
+    const uint32_t n_dg = spec->n_dst_groups, rw = (uint32_t)reach_row_words(spec->n_dst), cells = 4u * n_dg;
+    const uint32_t n_pair_rows = spec->n_svc * spec->n_src_groups;
+    std::fill(out_counts, out_counts + (size_t)n_pair_rows * cells, (uint64_t)0);
+    const GroupsPlan plan = groups_plan(spec->n_dst);
+    const GroupsPartition P = groups_partition(spec->src_group, spec->n_src, spec->n_src_groups, spec->dst_group, spec->n_dst,
+                                               plan.chunk_rows);
+    const uint32_t tiles = (rw + plan.tile_words - 1u) / plan.tile_words, phases = kGroupsBlock / plan.tile_words;
+    std::vector<uint32_t> acc(cells);
+    // every work item in order, its lanes as k_groups_count runs them; the accumulators go to
+    // out_counts after every item
+    for (uint32_t v = 0; v < spec->n_svc && spec->n_dst; v++)
+        for (const GroupsChunk& c : P.chunks)
+            for (uint32_t tile = 0; tile < tiles; tile++) {
+                std::fill(acc.begin(), acc.end(), 0u);
+                for (uint32_t lane = 0; lane < kGroupsBlock; lane++) {
+                    const uint32_t w = tile * plan.tile_words + lane % plan.tile_words, phase = lane / plan.tile_words;
+                    if (w >= rw || c.r0 + phase >= c.r1) continue;
+                    const uint32_t valid = diff_valid(spec->n_dst, w);
+                    const uint32_t* base = spec->matrix + (uint64_t)v * spec->n_src * rw + w;
+                    GroupsAcc a = {};
+                    uint32_t n = 0;
+                    for (uint32_t r = c.r0 + phase; r < c.r1; r += phases, n++) groups_add(a, base[(uint64_t)P.rows[r] * rw], valid);
+                    uint32_t gw[8];
+                    for (uint32_t k = 0; k < 8; k++) gw[k] = P.dgrp[16u * w + 2u * k] | (uint32_t)P.dgrp[16u * w + 2u * k + 1u] << 16;
+                    groups_flush(a, n, gw, [&](uint32_t g, uint32_t code, uint32_t cnt) { acc[4u * g + code] += cnt; });
+                }
+                uint64_t* out = out_counts + ((size_t)v * spec->n_src_groups + c.gs) * cells;
+                for (uint32_t i = 0; i < cells; i++) out[i] += acc[i];
+            }
+    // as k_groups_pack
+    const uint32_t rwo = (uint32_t)reach_row_words(n_dg);
+    for (uint32_t row = 0; out_packed && row < n_pair_rows; row++)
+        for (uint32_t jw = 0; jw < rwo; jw++)
+            out_packed[(size_t)row * rwo + jw] = groups_pack_word(out_counts + (size_t)row * cells, n_dg, jw);
+    return PG_OK;
+    GUARD_END(ctx)
+}
+
+int pg_debug_reach_groups_plan(pg_ctx* ctx, uint32_t n_dst, uint32_t* tile_words, uint32_t* chunk_rows) {
+    if (!ctx || !tile_words || !chunk_rows) return PG_EINVAL;
+    const GroupsPlan p = groups_plan(n_dst);
+    *tile_words = p.tile_words, *chunk_rows = p.chunk_rows;
     return PG_OK;
 }
 

@@ -394,6 +394,56 @@ def unpack_closure(packed, n):
     return unpack_reach(packed, 1, n, n)[0] == 2   # PG_CONN_ALLOW
 
 
+# ---- reachability groups (include/policygpu.h pg_reach_groups) -------------------------------
+GROUP_SKIP = _capi.GROUP_SKIP
+
+
+def groups_spec(matrix_ptr, n_svc, n_src, n_dst, src_group, dst_group, n_src_groups, n_dst_groups):
+    """pg_reach_groups_spec -> (spec, the arrays it points into: keep them alive for the call)"""
+    sg = np.ascontiguousarray(src_group, dtype=np.uint32)
+    dg = np.ascontiguousarray(dst_group, dtype=np.uint32)
+    if sg.shape != (n_src,) or dg.shape != (n_dst,):
+        raise ValueError("src_group / dst_group take one id per end point")
+    spec = _capi.pg_reach_groups_spec(matrix_ptr, int(n_svc), int(n_src), int(n_dst), sg.ctypes.data if n_src else None,
+                                      dg.ctypes.data if n_dst else None, int(n_src_groups), int(n_dst_groups))
+    return spec, (sg, dg)
+
+
+def reach_groups(engine, matrix, n_src, n_dst, src_group, dst_group, n_src_groups, n_dst_groups, packed=False,
+                 stream=None):
+    """A reach_matrix result summed into (src group, dst group) pairs, on the GPU (pg_reach_groups).
+    ``matrix`` is an int32 device tensor [n_svc, n_src, row_words(n_dst)]; ``src_group`` / ``dst_group``
+    give every end point a group id below its count, or GROUP_SKIP. -> (counts, packed): the cells of
+    every (service, src group, dst group) by ConnAction as an int64 tensor [n_svc, n_sg, n_dg, 4], and
+    with ``packed`` the GROUPS_* status of every pair as an int32 tensor [n_svc, n_sg, row_words(n_dg)]
+    in the audits' layout (unpack_groups, or reach_diff over two of them with n_cols = n_dg), else
+    None. The call never touches the hit counters."""
+    rw = reach_row_words(n_dst)
+    if matrix.dtype != torch.int32 or not matrix.is_contiguous() or matrix.numel() % max(1, n_src * rw):
+        raise ValueError("a contiguous int32 tensor [n_svc, n_src, row_words(n_dst)] expected")
+    n_svc = matrix.shape[0] if matrix.dim() == 3 else matrix.numel() // max(1, n_src * rw)
+    counts = torch.empty((n_svc, n_src_groups, n_dst_groups, 4), dtype=torch.int64, device="cuda")
+    status = torch.empty((n_svc, n_src_groups, reach_row_words(n_dst_groups)), dtype=torch.int32,
+                         device="cuda") if packed else None
+    if counts.numel() == 0:  # (an empty tensor has no address to hand over; the call would write nothing)
+        return counts, status
+    spec, keep = groups_spec(matrix.data_ptr() if matrix.numel() else None, n_svc, n_src, n_dst, src_group, dst_group,
+                             n_src_groups, n_dst_groups)
+    engine._ck(lib.pg_reach_groups(engine.h, C.byref(spec), counts.data_ptr(), status.data_ptr() if packed else None,
+                                   _stream_ptr(stream)))
+    del keep
+    return counts, status
+
+
+def unpack_groups(packed, n_dst_groups):
+    """packed group status words (tensor or array [..., row_words(n_dst_groups)]) -> uint8 GROUPS_*
+    [..., n_dst_groups]"""
+    if isinstance(packed, torch.Tensor):
+        packed = packed.cpu().numpy()
+    w = np.ascontiguousarray(packed).view(np.uint32)
+    return unpack_reach(w, 1, w.size // max(1, w.shape[-1]), n_dst_groups).reshape(w.shape[:-1] + (n_dst_groups,))
+
+
 def unpack(out_u32):
     w = out_u32.astype(np.uint32)
     return (w >> 30).astype(np.int64), (w & 0x3FFFFFFF).astype(np.int64)

@@ -530,6 +530,87 @@ class Engine:
         row, col, cb, ca = D.unpack_changes(changes)
         return [(pods[int(r)], pods[int(j)], int(x), int(y)) for r, j, x, y in zip(row, col, cb, ca)]
 
+    def debug_reach_groups_host(self, matrix, n_src, n_dst, src_group, dst_group, n_src_groups, n_dst_groups, packed=True):
+        """TESTS ONLY: pg_reach_groups's per-word code run on the host (pg_debug_reach_groups_host)
+        over a numpy array of packed words [n_svc, n_src, row_words(n_dst)]. -> (counts u64 [n_svc,
+        n_sg, n_dg, 4], status words u32 [n_svc, n_sg, row_words(n_dg)] or None); the outputs are
+        pre-filled with 0xFF.."""
+        import numpy as np
+        from . import device as D
+        m = np.ascontiguousarray(matrix, dtype=np.uint32)
+        n_svc = m.shape[0] if m.ndim == 3 else m.size // max(1, n_src * lib.pg_reach_row_words(n_dst))
+        counts = np.full((n_svc, n_src_groups, n_dst_groups, 4), 0xFFFFFFFFFFFFFFFF, np.uint64)
+        status = np.full((n_svc, n_src_groups, lib.pg_reach_row_words(n_dst_groups)), 0xFFFFFFFF, np.uint32) if packed else None
+        if counts.size == 0:
+            return counts, status
+        p = lambda x: x.ctypes.data_as(C.c_void_p)
+        spec, keep = D.groups_spec(m.ctypes.data if m.size else None, n_svc, n_src, n_dst, src_group, dst_group,
+                                   n_src_groups, n_dst_groups)
+        self._ck(lib.pg_debug_reach_groups_host(self.h, C.byref(spec), p(counts), p(status) if packed else None))
+        del keep
+        return counts, status
+
+    def debug_reach_groups_plan(self, n_dst):
+        """TESTS ONLY: how pg_reach_groups cuts rows of n_dst cells (pg_debug_reach_groups_plan) ->
+        {tile_words, chunk_rows}"""
+        t, c = C.c_uint32(), C.c_uint32()
+        self._ck(lib.pg_debug_reach_groups_plan(self.h, int(n_dst), C.byref(t), C.byref(c)))
+        return {"tile_words": t.value, "chunk_rows": c.value}
+
+    def _groups(self, src_groups, dst_groups, services, host):
+        """one pg_reach_matrix over the groups' pods, listed once per group they are in, and one
+        pg_reach_groups -> (counts u64 [n_svc, n_sg, n_dg, 4], status words [n_svc, n_sg,
+        row_words(n_dg)]), device tensors or with ``host`` numpy arrays"""
+        import numpy as np
+        from . import device as D
+        src = [ip for pods in src_groups.values() for ip in self._pod_ips(pods)]
+        dst = [ip for pods in dst_groups.values() for ip in self._pod_ips(pods)]
+        sg = np.repeat(np.arange(len(src_groups), dtype=np.uint32), [len(p) for p in src_groups.values()])
+        dg = np.repeat(np.arange(len(dst_groups), dtype=np.uint32), [len(p) for p in dst_groups.values()])
+        if host:
+            m = self.debug_reach_matrix_host(src, dst, services, words=False)
+            return self.debug_reach_groups_host(m, len(src), len(dst), sg, dg, len(src_groups), len(dst_groups))
+        m = D.reach_matrix(self, src, dst, services)
+        return D.reach_groups(self, m, len(src), len(dst), sg, dg, len(src_groups), len(dst_groups), packed=True)
+
+    def reachability_groups(self, src_groups, dst_groups, services, host=False):
+        """Which groups reach which, and how fully: ``src_groups`` / ``dst_groups`` are ordered mappings
+        from a name (a namespace, a deployment, a label set) to a list of pods; a pod may be in several
+        groups. One pg_reach_matrix and one pg_reach_groups. -> (counts uint64 [n_svc, n_sg, n_dg, 4]:
+        the (src pod, dst pod) cells of every (service, src group, dst group) by ConnAction, status
+        uint8 [n_svc, n_sg, n_dg]: GROUPS_NONE / SOME / ALL of them ALLOW, or GROUPS_EMPTY) in the
+        mappings' order. Pods and services as in reachability. ``host``: TESTS ONLY, the host twins."""
+        import numpy as np
+        from . import device as D
+        n_sg, n_dg = len(src_groups), len(dst_groups)
+        if not services or not n_sg or not n_dg:
+            return np.zeros((len(services), n_sg, n_dg, 4), np.uint64), np.zeros((len(services), n_sg, n_dg), np.uint8)
+        counts, status = self._groups(src_groups, dst_groups, services, host)
+        if not host:
+            counts = counts.cpu().numpy().view(np.uint64)
+        return counts, D.unpack_groups(status, n_dg)
+
+    def reachability_groups_diff(self, baseline, src_groups, dst_groups, services, host=False):
+        """Which group pairs a policy change moved: the (service, src group, dst group) whose status
+        under this engine differs from that under ``baseline`` (another Engine on the same device), by
+        two pg_reach_matrix calls, two pg_reach_groups calls and one pg_reach_diff over the summaries.
+        -> [(service index, src group, dst group, status before, after), ...] in (service, src group,
+        dst group) order with the names as given. ``host``: TESTS ONLY, the host twins."""
+        from . import device as D
+        n_sg, n_dg = len(src_groups), len(dst_groups)
+        if not services or not n_sg or not n_dg:
+            return []
+        _, b = baseline._groups(src_groups, dst_groups, services, host)
+        _, a = self._groups(src_groups, dst_groups, services, host)
+        if host:
+            k, changes, _, _ = self.debug_reach_diff_host(b, a, n_dg, row_changes=False)
+            changes = changes[:k]
+        else:
+            _, changes, _, _ = D.reach_diff(self, b, a, n_dg)
+        row, col, cb, ca = D.unpack_changes(changes)
+        sn, dn = list(src_groups), list(dst_groups)
+        return [(int(r) // n_sg, sn[int(r) % n_sg], dn[int(j)], int(x), int(y)) for r, j, x, y in zip(row, col, cb, ca)]
+
     def debug_walk_stats(self, table_id, src, dst, dport, proto):
         """MEASUREMENT: per tuple, the loads a SINGLE launch on table_id makes of the table's
         structure (pg_debug_walk_stats) -> (lds_reads u32[n], mem_reads u32[n], launch STAGE)"""
