@@ -708,6 +708,67 @@ int pg_debug_reach_groups_host(pg_ctx* ctx, const pg_reach_groups_spec* spec, ui
  * rows of one src group it walks between two flushes. Launches nothing. */
 int pg_debug_reach_groups_plan(pg_ctx* ctx, uint32_t n_dst, uint32_t* tile_words, uint32_t* chunk_rows);
 
+/* ---- reachability paths: shortest attack paths and choke points, on the device -------------
+ * "Pod A gets to the database in 3 hops -- through which pods? Which pod do most of those paths pass
+ * through?" The input is a pg_reach_closure out_hops (n x n uint16_t, row-major, 0 = not reachable),
+ * which stays on the device; a matrix taken with max_hops = k is valid, cells beyond k are simply
+ * unreachable. edge(a, b) <=> hops(a, b) == 1.
+ *   Path of a query (i, j), d = hops(i, j): none when d == 0; else p_0 = i .. p_d = j with, for t = d,
+ *   d - 1, .., 2, p_{t-1} = the least k with hops(i, k) == t - 1 and hops(k, p_t) == 1 (the "least
+ *   predecessor": it depends on (i, p_t) only, so the paths of one src form a tree). i == j asks for
+ *   the shortest cycle through i and is walked the same way. The intermediates p_1 .. p_{d-1} are
+ *   pairwise distinct and differ from i and j.
+ *   Over an input that no closure wrote, a step may find no k: the query is *broken* -- out_len 0,
+ *   its nodes row all 0xFFFF, counted in n_broken; out_via is then unspecified. On any input the
+ *   call ends and stays inside its arrays.
+ *   out_len    device, required, n_queries uint16_t at the queries' own positions: d, and 0 for a
+ *              query that is unreachable or broken
+ *   out_nodes  device, optional, n_queries rows of max_len + 1 uint16_t: p_0 .. p_d, then 0xFFFF. A
+ *              path with d > max_len is *too long*: its row is all 0xFFFF, and it still counts in
+ *              out_len and out_via. Every entry of every row is written
+ *   out_via    device, optional, n words: out_via[k] = the queries whose path has k among its
+ *              intermediates -- the choke points. Every word is written (the call clears the array
+ *              on the stream first). Integer sums: exact, and the same on every run
+ *   result     host, required
+ * Duplicate queries are answered each at its position. Like pg_reach_closure the call reads no table
+ * and triggers no compile, and it never touches the hit counters or their snapshots; ctx only names
+ * the device and its launch knobs. It sorts the queries by src on the host, copies them in, enqueues
+ * in order on hip_stream (the transposed edge bits of hops into scratch, then the walk) and
+ * synchronises that stream. n_queries == 0: PG_OK, *result zeroed, out_via cleared when given,
+ * nothing else written (with n == 0 as well, nothing on the device). PG_EINVAL (pg_last_error says
+ * which argument, and for a bad id which index): a null spec, hops, out_len or result; a null src or
+ * dst with queries; n above 2^15; n_queries above 2^24; an id >= n; with out_nodes, max_len 0 or above
+ * 2^15, or n_queries * (max_len + 1) >= 2^32. PG_ENOMEM: the scratch allocation (n x n bits and the
+ * sorted queries) failed. */
+typedef struct pg_reach_paths_spec {
+    const uint16_t* hops;   /* device, n * n: a pg_reach_closure out_hops; 2-B aligned, nothing more assumed */
+    uint32_t n;             /* end points, 1 .. 2^15 */
+    const uint32_t* src;    /* host, n_queries entries, each < n; duplicates allowed, any order */
+    const uint32_t* dst;    /* host, likewise */
+    uint64_t n_queries;     /* 0 .. 2^24 */
+    uint32_t max_len;       /* with out_nodes: the longest path (edges) that is written, 1 .. 2^15 */
+} pg_reach_paths_spec;
+typedef struct pg_reach_paths_result {   /* host */
+    uint64_t n_found;       /* queries with a path (out_len != 0) */
+    uint64_t n_unreachable; /* hops(i, j) == 0 */
+    uint64_t n_too_long;    /* found, but longer than max_len: a subset of n_found; 0 without out_nodes */
+    uint64_t n_broken;      /* n_found + n_unreachable + n_broken == n_queries */
+    uint64_t n_via;         /* sum of out_via = intermediates over all found paths */
+    uint32_t longest;       /* largest out_len */
+} pg_reach_paths_result;
+int pg_reach_paths(pg_ctx* ctx, const pg_reach_paths_spec* spec, uint16_t* out_len, uint16_t* out_nodes,
+                   uint32_t* out_via, pg_reach_paths_result* result, void* hip_stream);
+/* TESTS ONLY -- never on the audit path: pg_reach_paths's per-word code, partition and plan
+ * (paths.hpp, the functions the kernels and the launch call) on the host, work item by work item;
+ * hops, out_len, out_nodes and out_via are host arrays. Does not touch the device. */
+int pg_debug_reach_paths_host(pg_ctx* ctx, const pg_reach_paths_spec* spec, uint16_t* out_len, uint16_t* out_nodes,
+                              uint32_t* out_via, pg_reach_paths_result* result);
+/* TESTS ONLY: how a pg_reach_paths over n end points is cut, from the one function the launch itself
+ * uses (paths.hpp paths_plan): the most queries of one src a work item holds, and the most LDS a
+ * workgroup takes (the staged row of hops, the counters and, where they fit, the out_via counts).
+ * Launches nothing. */
+int pg_debug_reach_paths_plan(pg_ctx* ctx, uint32_t n, uint32_t* chunk_queries, uint32_t* lds_bytes);
+
 /* ---- policy configurator ------------------------------------------
  * configurator.PolicyConfiguratorAPI / Txn (plugins/policy/configurator/configurator_api.go:28-54,
  * configurator_impl.go:104-472): K8s-shaped policies per pod -> ordered ContivRule lists

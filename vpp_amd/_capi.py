@@ -121,6 +121,16 @@ class pg_reach_groups_spec(C.Structure):
                 ("n_dst_groups", C.c_uint32)]
 
 
+class pg_reach_paths_spec(C.Structure):
+    _fields_ = [("hops", C.c_void_p), ("n", C.c_uint32), ("src", C.c_void_p), ("dst", C.c_void_p),
+                ("n_queries", C.c_uint64), ("max_len", C.c_uint32)]
+
+
+class pg_reach_paths_result(C.Structure):
+    _fields_ = [("n_found", C.c_uint64), ("n_unreachable", C.c_uint64), ("n_too_long", C.c_uint64),
+                ("n_broken", C.c_uint64), ("n_via", C.c_uint64), ("longest", C.c_uint32)]
+
+
 class pg_pod_id(C.Structure):
     _fields_ = [("ns", C.c_char_p), ("name", C.c_char_p)]
 
@@ -282,6 +292,10 @@ _SIGS = {
     "pg_reach_groups": (C.c_int, [_P, C.POINTER(pg_reach_groups_spec), _P, _P, _P]),
     "pg_debug_reach_groups_host": (C.c_int, [_P, C.POINTER(pg_reach_groups_spec), _P, _P]),
     "pg_debug_reach_groups_plan": (C.c_int, [_P, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "pg_reach_paths": (C.c_int, [_P, C.POINTER(pg_reach_paths_spec), _P, _P, _P, C.POINTER(pg_reach_paths_result), _P]),
+    "pg_debug_reach_paths_host": (C.c_int, [_P, C.POINTER(pg_reach_paths_spec), _P, _P, _P,
+                                            C.POINTER(pg_reach_paths_result)]),
+    "pg_debug_reach_paths_plan": (C.c_int, [_P, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "pg_session_rules_new": (_P, [C.c_char_p]),
     "pg_session_rules_free": (None, [_P]),
     "pg_session_rules_clear": (C.c_int, [_P]),

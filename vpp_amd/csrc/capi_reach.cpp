@@ -1,5 +1,6 @@
 // extern "C" boundary of the reachability audits (include/policygpu.h): the matrix, the port sweep,
-// the diff, the closure and the groups, each with the host twin the tests compare its kernels to.
+// the diff, the closure, the groups and the paths, each with the host twin the tests compare its
+// kernels to.
 #include <algorithm>
 #include <numeric>
 
@@ -7,6 +8,7 @@
 #include "closure.hpp"
 #include "diff.hpp"
 #include "groups.hpp"
+#include "paths.hpp"
 #include "ports.hpp"
 
 using namespace pg;
@@ -593,6 +595,129 @@ int pg_debug_reach_groups_plan(pg_ctx* ctx, uint32_t n_dst, uint32_t* tile_words
     if (!ctx || !tile_words || !chunk_rows) return PG_EINVAL;
     const GroupsPlan p = groups_plan(n_dst);
     *tile_words = p.tile_words, *chunk_rows = p.chunk_rows;
+    return PG_OK;
+}
+
+}  // extern "C"
+
+// ---- reachability paths (paths.hpp) --------------------------------------------------------------
+namespace {
+static_assert(sizeof(pg_reach_paths_result) == sizeof(PathsResult), "pg_reach_paths_result is paths.hpp's PathsResult");
+
+// argument checks shared by pg_reach_paths and its host twin: PG_OK with *result zeroed
+int paths_args(pg_ctx* ctx, const pg_reach_paths_spec* spec, const uint16_t* out_len, const uint16_t* out_nodes,
+               pg_reach_paths_result* result) {
+    if (!ctx) return PG_EINVAL;
+    if (!spec || !spec->hops || !out_len || !result) return fail(ctx, PG_EINVAL, "null spec, hops, out_len or result");
+    if (spec->n > kPathsMaxN) return fail(ctx, PG_EINVAL, "more than 2^15 end points");
+    if (spec->n_queries > kPathsMaxQueries) return fail(ctx, PG_EINVAL, "n_queries above 2^24");
+    if (spec->n_queries && (!spec->src || !spec->dst)) return fail(ctx, PG_EINVAL, "null src or dst");
+    if (out_nodes) {
+        if (!spec->max_len || spec->max_len > kPathsMaxLen) return fail(ctx, PG_EINVAL, "max_len is 0 or above 2^15");
+        if (spec->n_queries * ((uint64_t)spec->max_len + 1u) >> 32)
+            return fail(ctx, PG_EINVAL, "n_queries * (max_len + 1) reaches 2^32");
+    }
+    auto ids = [&](const char* what, const uint32_t* a) {
+        for (uint64_t q = 0; q < spec->n_queries; q++)
+            if (a[q] >= spec->n)
+                return fail(ctx, PG_EINVAL, std::string(what) + "[" + std::to_string(q) + "] = " + std::to_string(a[q]) +
+                                                " is not below n = " + std::to_string(spec->n));
+        return (int)PG_OK;
+    };
+    if (int rc = ids("src", spec->src)) return rc;
+    if (int rc = ids("dst", spec->dst)) return rc;
+    *result = pg_reach_paths_result{0, 0, 0, 0, 0, 0};
+    return PG_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int pg_reach_paths(pg_ctx* ctx, const pg_reach_paths_spec* spec, uint16_t* out_len, uint16_t* out_nodes, uint32_t* out_via,
+                   pg_reach_paths_result* result, void* stream) {
+    GUARD_BEGIN
+    if (int rc = paths_args(ctx, spec, out_len, out_nodes, result)) return rc;
+    if (!spec->n) return PG_OK;  // (then there is no query either)
+    if (!spec->n_queries && !out_via) return PG_OK;
+    DEVICE_GUARD(ctx);
+    PathsPartition part;
+    if (spec->n_queries) part = paths_partition(spec->src, spec->dst, spec->n_queries, spec->n, paths_plan(spec->n).chunk_queries);
+    const PathsSpecDev sd{spec->hops, spec->n, spec->max_len, spec->n_queries, spec->n_queries ? &part : nullptr};
+    std::string err;
+    PathsResult r{0, 0, 0, 0, 0, 0};
+    const int rc = dev_reach_paths(ctx->eng.tune.blocks_per_cu, sd, out_len, out_nodes, out_via, &r, stream, &err);
+    if (rc != 0) return fail(ctx, rc == -2 ? PG_ENOMEM : PG_EIO, err);
+    *result = pg_reach_paths_result{r.n_found, r.n_unreachable, r.n_too_long, r.n_broken, r.n_via, r.longest};
+    return PG_OK;
+    GUARD_END(ctx)
+}
+
+int pg_debug_reach_paths_host(pg_ctx* ctx, const pg_reach_paths_spec* spec, uint16_t* out_len, uint16_t* out_nodes,
+                              uint32_t* out_via, pg_reach_paths_result* result) {
+    GUARD_BEGIN
+    if (int rc = paths_args(ctx, spec, out_len, out_nodes, result)) return rc;
+    const uint32_t n = spec->n, stride = closure_stride(n), bw = closure_bit_words(n);
+    if (out_via) std::fill(out_via, out_via + n, 0u);
+    if (!spec->n_queries) return PG_OK;
+    const uint32_t max_len = out_nodes ? spec->max_len : 0u;
+    // the transposed edge bits, as k_paths_edges_t's lanes build them
+    std::vector<uint32_t> ET((size_t)n * stride, 0u);
+    for (uint32_t c = 0; c < n; c++)
+        for (uint32_t w = 0; w < stride; w++) ET[(size_t)c * stride + w] = paths_edge_word(spec->hops, n, c, w);
+    const PathsPartition P = paths_partition(spec->src, spec->dst, spec->n_queries, n, paths_plan(n).chunk_queries);
+    pg_reach_paths_result r{0, 0, 0, 0, 0, 0};
+    // every work item in order, its queries as k_paths_walk's waves run them: passes of 64 lanes, the
+    // lowest lane with a match
+    for (const PathsItem& item : P.items) {
+        const uint16_t* row = spec->hops + (size_t)item.src * n;
+        for (uint32_t q = item.q0; q < item.q1; q++) {
+            const uint32_t j = P.dst[q], o = P.pos[q], d = row[j];
+            const bool fits = d <= max_len;
+            uint16_t* nrow = out_nodes ? out_nodes + (size_t)o * (max_len + 1u) : nullptr;
+            bool broken = false;
+            uint32_t cur = j;
+            for (uint32_t t = d; t >= 2u && !broken; t--) {
+                const uint32_t* et = &ET[(size_t)cur * stride];
+                uint32_t k = kPathsNoPred;
+                for (uint32_t wp = 0; wp < bw && k == kPathsNoPred; wp += kPathsPassWords)
+                    for (uint32_t lane = 0; lane < 64u && k == kPathsNoPred; lane++) {
+                        const uint32_t w = wp + lane;
+                        k = paths_word_pred(w < bw ? et[w] : 0u, w, row, t - 1u);
+                    }
+                if (k == kPathsNoPred) {
+                    broken = true;
+                    break;
+                }
+                if (nrow && fits) paths_store(nrow, t - 1u, k);
+                if (out_via) out_via[k]++;
+                cur = k;
+            }
+            const bool found = d != 0u && !broken;
+            out_len[o] = (uint16_t)(found ? d : 0u);
+            if (nrow) {
+                const bool written = found && fits;
+                if (written) paths_store(nrow, 0u, item.src), paths_store(nrow, d, j);
+                paths_fill(nrow, written ? d + 1u : 0u, max_len + 1u, 0u, 1u);
+            }
+            if (found) {
+                r.n_found++, r.n_via += d - 1u, r.longest = std::max(r.longest, d);
+                if (nrow && !fits) r.n_too_long++;
+            } else if (broken) {
+                r.n_broken++;
+            } else {
+                r.n_unreachable++;
+            }
+        }
+    }
+    *result = r;
+    return PG_OK;
+    GUARD_END(ctx)
+}
+
+int pg_debug_reach_paths_plan(pg_ctx* ctx, uint32_t n, uint32_t* chunk_queries, uint32_t* lds_bytes) {
+    if (!ctx || !chunk_queries || !lds_bytes) return PG_EINVAL;
+    const PathsPlan p = paths_plan(n);
+    *chunk_queries = p.chunk_queries, *lds_bytes = p.lds_bytes;
     return PG_OK;
 }
 

@@ -444,6 +444,67 @@ def unpack_groups(packed, n_dst_groups):
     return unpack_reach(w, 1, w.size // max(1, w.shape[-1]), n_dst_groups).reshape(w.shape[:-1] + (n_dst_groups,))
 
 
+# ---- reachability paths (include/policygpu.h pg_reach_paths) ---------------------------------
+PATHS_NONE = 0xFFFF   # a nodes entry behind the path; every entry of a row without one
+
+
+def paths_spec(hops_ptr, n, src, dst, max_len):
+    """pg_reach_paths_spec -> (spec, the arrays it points into: keep them alive for the call)"""
+    s = np.ascontiguousarray(src, dtype=np.uint32)
+    d = np.ascontiguousarray(dst, dtype=np.uint32)
+    if s.ndim != 1 or s.shape != d.shape:
+        raise ValueError("src and dst take one id per query")
+    spec = _capi.pg_reach_paths_spec(hops_ptr, int(n), s.ctypes.data if s.size else None, d.ctypes.data if s.size else None,
+                                     s.size, int(max_len))
+    return spec, (s, d)
+
+
+def paths_result(res):
+    return {"n_found": res.n_found, "n_unreachable": res.n_unreachable, "n_too_long": res.n_too_long,
+            "n_broken": res.n_broken, "n_via": res.n_via, "longest": res.longest}
+
+
+def reach_paths(engine, hops, n, src, dst, max_len=None, nodes=True, via=False, stream=None):
+    """One shortest path per (src, dst) query over a reach_closure ``hops`` tensor (int16 [n, n], on the
+    device), and the choke points, on the GPU (pg_reach_paths). The path of a query is the one the
+    least-predecessor rule of include/policygpu.h defines. -> (lengths, nodes, via, result): the edges
+    of every path as an int16 tensor [n_queries] (0 = unreachable or broken), with ``nodes`` the paths
+    as an int16 tensor [n_queries, max_len + 1] (p_0 .. p_d, then PATHS_NONE; unpack_paths) else None,
+    with ``via`` the number of paths that pass through every end point as an int32 tensor [n] else
+    None, and {n_found, n_unreachable, n_too_long, n_broken, n_via, longest}. ``max_len`` None: n, which
+    no shortest path exceeds. The call never touches the hit counters."""
+    if hops.dtype != torch.int16 or not hops.is_contiguous() or hops.numel() != n * n:
+        raise ValueError("a contiguous int16 tensor [n, n] expected")
+    max_len = max(1, n) if max_len is None else int(max_len)
+    spec, keep = paths_spec(hops.data_ptr(), n, src, dst, max_len)
+    nq = int(spec.n_queries)
+    lens = torch.empty(nq, dtype=torch.int16, device="cuda")
+    rows = torch.empty((nq, max_len + 1), dtype=torch.int16, device="cuda") if nodes else None
+    cnt = torch.empty(n, dtype=torch.int32, device="cuda") if via else None
+    res = _capi.pg_reach_paths_result()
+    if n == 0 or (nq == 0 and not via):  # (an empty tensor has no address to hand over; the call would write nothing)
+        return lens, rows, cnt, paths_result(res)
+    # (without a query out_len has no entry: any address that is not null will do)
+    engine._ck(lib.pg_reach_paths(engine.h, C.byref(spec), lens.data_ptr() if nq else hops.data_ptr(),
+                                  rows.data_ptr() if nodes and nq else None, cnt.data_ptr() if via else None,
+                                  C.byref(res), _stream_ptr(stream)))
+    del keep
+    return lens, rows, cnt, paths_result(res)
+
+
+def unpack_paths(lengths, nodes):
+    """path lengths [n_queries] and nodes rows [n_queries, max_len + 1] (tensors or arrays) -> one list of
+    node indices per query, None where the query has no path or the path is too long for its row"""
+    if isinstance(lengths, torch.Tensor):
+        lengths = lengths.cpu().numpy()
+    if isinstance(nodes, torch.Tensor):
+        nodes = nodes.cpu().numpy()
+    d = np.ascontiguousarray(lengths).view(np.uint16)
+    rows = np.ascontiguousarray(nodes).view(np.uint16)
+    return [rows[q, :int(d[q]) + 1].tolist() if d[q] and d[q] < rows.shape[1] and rows[q, 0] != PATHS_NONE else None
+            for q in range(d.size)]
+
+
 def unpack(out_u32):
     w = out_u32.astype(np.uint32)
     return (w >> 30).astype(np.int64), (w & 0x3FFFFFFF).astype(np.int64)

@@ -508,27 +508,116 @@ class Engine:
             hop = hop.cpu().numpy().view(np.uint16)
         return D.unpack_closure(packed, n), hop, res["levels"]
 
-    def reachability_closure_diff(self, baseline, pods, services, transitions=_capi.DIFF_OPENED, max_hops=0, host=False):
+    def reachability_closure_diff(self, baseline, pods, services, transitions=_capi.DIFF_OPENED, max_hops=0, host=False,
+                                  paths=False):
         """What a policy change opened (or closed) transitively: the (src pod, dst pod) whose cell of
         the closure under this engine differs from that under ``baseline`` (another Engine on the same
         device), by two pg_reach_matrix calls, two pg_reach_closure calls and one pg_reach_diff over
         the closures. -> [(src pod, dst pod, before, after), ...] in (src, dst) order with the pods as
-        given; before / after are ConnActions, ALLOW = reachable and DENY_SYN = not. ``host``: TESTS
-        ONLY, the host twins."""
+        given; before / after are ConnActions, ALLOW = reachable and DENY_SYN = not. With ``paths`` every
+        entry has a fifth member: for a cell that is reachable after, its path under this engine as a
+        list of pods (one pg_reach_paths call, the diff's changes being the queries), else None.
+        ``host``: TESTS ONLY, the host twins."""
         from . import device as D
         ips = self._pod_ips(pods)
         n = len(ips)
         if n == 0 or not services:
             return []
         b, _, _ = baseline._closure(ips, services, max_hops, host, False)
-        a, _, _ = self._closure(ips, services, max_hops, host, False)
+        a, hop, _ = self._closure(ips, services, max_hops, host, paths)
         if host:
             k, changes, _, _ = self.debug_reach_diff_host(b, a, n, transitions, row_changes=False)
             changes = changes[:k]
         else:
             _, changes, _, _ = D.reach_diff(self, b, a, n, transitions)
         row, col, cb, ca = D.unpack_changes(changes)
-        return [(pods[int(r)], pods[int(j)], int(x), int(y)) for r, j, x, y in zip(row, col, cb, ca)]
+        out = [(pods[int(r)], pods[int(j)], int(x), int(y)) for r, j, x, y in zip(row, col, cb, ca)]
+        if not paths:
+            return out
+        found = self._paths(hop, n, row, col, host)
+        return [t + (None if p is None else [pods[k] for k in p],) for t, p in zip(out, found)]
+
+    def debug_reach_paths_host(self, hops, n, src, dst, max_len=None, nodes=True, via=True):
+        """TESTS ONLY: pg_reach_paths's per-word code, partition and plan run on the host
+        (pg_debug_reach_paths_host) over a numpy array of hop counts [n, n]. -> (lengths u16 [n_queries],
+        nodes u16 [n_queries, max_len + 1] or None, via u32 [n] or None, {n_found, ...}); the outputs are
+        pre-filled with 0xFF.. (the nodes with 0xEEEE)."""
+        import numpy as np
+        from . import device as D
+        h = np.ascontiguousarray(hops, dtype=np.uint16)
+        max_len = max(1, n) if max_len is None else int(max_len)
+        spec, keep = D.paths_spec(h.ctypes.data, n, src, dst, max_len)
+        nq = int(spec.n_queries)
+        lens = np.full(nq, 0xFFFF, np.uint16)
+        rows = np.full((nq, max_len + 1), 0xEEEE, np.uint16) if nodes else None
+        cnt = np.full(n, 0xFFFFFFFF, np.uint32) if via else None
+        res = _capi.pg_reach_paths_result()
+        if n == 0:
+            return lens, rows, cnt, D.paths_result(res)
+        p = lambda x: x.ctypes.data_as(C.c_void_p)
+        self._ck(lib.pg_debug_reach_paths_host(self.h, C.byref(spec), p(lens) if nq else p(h), p(rows) if nodes and nq else None,
+                                               p(cnt) if via else None, C.byref(res)))
+        del keep
+        return lens, rows, cnt, D.paths_result(res)
+
+    def debug_reach_paths_plan(self, n):
+        """TESTS ONLY: how pg_reach_paths over n end points is cut (pg_debug_reach_paths_plan) ->
+        {chunk_queries, lds_bytes}"""
+        c, b = C.c_uint32(), C.c_uint32()
+        self._ck(lib.pg_debug_reach_paths_plan(self.h, int(n), C.byref(c), C.byref(b)))
+        return {"chunk_queries": c.value, "lds_bytes": b.value}
+
+    def _paths(self, hop, n, src, dst, host, via=False):
+        """one pg_reach_paths over a _closure's hops (a device tensor, or with ``host`` a numpy array) ->
+        one list of node indices per query, None where there is no path; with ``via`` the uint32 counts
+        [n] instead"""
+        import numpy as np
+        from . import device as D
+        if host:
+            lens, rows, cnt, _ = self.debug_reach_paths_host(hop, n, src, dst, nodes=not via, via=via)
+        else:
+            lens, rows, cnt, _ = D.reach_paths(self, hop, n, src, dst, nodes=not via, via=via)
+            if via:
+                cnt = cnt.cpu().numpy().view(np.uint32)
+        return cnt if via else D.unpack_paths(lens, rows)
+
+    def reachability_paths(self, pods, services, pairs, max_hops=0, host=False):
+        """Through which pods: for every (src pod, dst pod) of ``pairs``, both among ``pods``, one
+        shortest path over the graph of reachability_closure, by one pg_reach_matrix over pods x pods,
+        one pg_reach_closure and one pg_reach_paths. -> one list of pods per pair, from the src to the
+        dst (a pod paired with itself: its shortest cycle), None where the dst is not reachable (within
+        ``max_hops`` edges when that is set). Of several shortest paths it is the one the
+        least-predecessor rule of include/policygpu.h defines, in the order of ``pods``. Pods and
+        services as in reachability. ``host``: TESTS ONLY, the host twins."""
+        ips = self._pod_ips(pods)
+        n = len(ips)
+        pairs = list(pairs)
+        if n == 0 or not services or not pairs:
+            return [None] * len(pairs)
+        index = {pod: k for k, pod in reversed(list(enumerate(pods)))}
+        src, dst = [index[a] for a, _ in pairs], [index[b] for _, b in pairs]
+        _, hop, _ = self._closure(ips, services, max_hops, host, True)
+        found = self._paths(hop, n, src, dst, host)
+        return [None if p is None else [pods[k] for k in p] for p in found]
+
+    def reachability_chokepoints(self, pods, services, sources=None, targets=None, max_hops=0, host=False):
+        """Which pod to lock down: over the shortest paths (as reachability_paths picks them) from every
+        pod of ``sources`` to every pod of ``targets`` (both among ``pods``; None = all of them), how many
+        pass through each pod, by one pg_reach_matrix, one pg_reach_closure and one pg_reach_paths that
+        returns the counts alone. -> [(pod, count), ...] of the pods with a count, by descending count and
+        then in the order of ``pods``. ``host``: TESTS ONLY, the host twins."""
+        import numpy as np
+        ips = self._pod_ips(pods)
+        n = len(ips)
+        if n == 0 or not services:
+            return []
+        index = {pod: k for k, pod in reversed(list(enumerate(pods)))}
+        s = np.arange(n, dtype=np.uint32) if sources is None else np.array([index[p] for p in sources], np.uint32)
+        t = np.arange(n, dtype=np.uint32) if targets is None else np.array([index[p] for p in targets], np.uint32)
+        _, hop, _ = self._closure(ips, services, max_hops, host, True)
+        cnt = self._paths(hop, n, np.repeat(s, t.size), np.tile(t, s.size), host, via=True)
+        order = np.argsort(-cnt.astype(np.int64), kind="stable")
+        return [(pods[int(k)], int(cnt[k])) for k in order if cnt[k]]
 
     def debug_reach_groups_host(self, matrix, n_src, n_dst, src_group, dst_group, n_src_groups, n_dst_groups, packed=True):
         """TESTS ONLY: pg_reach_groups's per-word code run on the host (pg_debug_reach_groups_host)
