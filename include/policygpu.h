@@ -185,7 +185,10 @@ int pg_ctx_device(const pg_ctx* ctx);
  * -- for tables the cross product cannot take, default 1; 0 = candidate lists; 2 = wherever it
  * fits, for tests), "launch_max_tuples" (a pg_classify batch larger than this takes several
  * kernel launches of at most this many tuples, in order on the stream; a multiple of 64, 0 =
- * the largest a launch's 32-bit stream offsets allow, 2^30 - 64; default 0).
+ * the largest a launch's 32-bit stream offsets allow, 2^30 - 64; default 0), "classes_hash_bits"
+ * (pg_reach_classes keeps only this many low bits of every signature, 0..64, 0 = every signature
+ * equal; the result does not depend on it, only the rounds of the equality check do -- for tests
+ * that reach those rounds at small shapes; default 64).
  * pg_ctx_set_tuning sets one context's knob; pg_set_tuning sets the process default that
  * contexts created afterwards start from. PG_EINVAL for an unknown key or a value out of range. */
 int pg_ctx_set_tuning(pg_ctx* ctx, const char* key, int value);
@@ -768,6 +771,68 @@ int pg_debug_reach_paths_host(pg_ctx* ctx, const pg_reach_paths_spec* spec, uint
  * workgroup takes (the staged row of hops, the counters and, where they fit, the out_via counts).
  * Launches nothing. */
 int pg_debug_reach_paths_plan(pg_ctx* ctx, uint32_t n, uint32_t* chunk_queries, uint32_t* lds_bytes);
+
+/* ---- reachability classes: the end points the policy treats identically, on the device -----
+ * "Which pods does the policy treat as one role, and which replica differs from its siblings?" The
+ * input is a pg_reach_matrix out_packed (n_svc * n_src rows of pg_reach_row_words(n_dst) words), which
+ * stays on the device in its 2 bits per cell.
+ *   Equality: src end points i, i' are equal when cell(v, i, j) == cell(v, i', j) for every slice v and
+ *   every j; dst end points j, j' are equal when cell(v, i, j) == cell(v, i, j') for every v and i. All
+ *   four ConnAction codes count, not only ALLOW. A duplicate end point is an equal end point.
+ *   Classes: the equivalence classes of those relations, by equality and not by hash: the call
+ *   compares 64-bit signatures first and then checks every candidate cell for cell, so the result is
+ *   right even when two different signatures share a hash.
+ *   Numbering by first appearance: the class of the least end point not yet classed gets the next id,
+ *   from 0. So class[0] == 0, the representatives (the least members) ascend, and the ids depend on
+ *   nothing but the input.
+ *   out_src_class  device, optional, n_src words: the class of every src end point
+ *   out_dst_class  device, optional, n_dst words. At least one of the two is given; a side that is not
+ *                  asked for is not computed
+ *   out_src_rep    device, optional, capacity n_src words: the first n_src_classes entries are each
+ *   out_dst_rep    class's least member; entries past that are not written. Likewise n_dst /
+ *                  n_dst_classes. Ignored for a side whose class output is null
+ *   out_quotient   device, optional, needs both class outputs; capacity that of the input, n_svc *
+ *                  n_src * pg_reach_row_words(n_dst) words. The first n_svc * n_src_classes *
+ *                  pg_reach_row_words(n_dst_classes) words are the matrix of the representatives in
+ *                  the audits' layout: cell (v, cs, cd) = cell(v, src_rep[cs], dst_rep[cd]), the
+ *                  padding bits of a row's last word zero; nothing past that is written. A valid
+ *                  before / after of pg_reach_diff, and what pg_reach_groups over the two class
+ *                  arrays gives as the single non-zero code of every pair
+ *   result         host, required
+ * The padding bits of the input rows are masked, never trusted. Like pg_reach_diff the call reads no
+ * table and triggers no compile, and it never touches the hit counters or their snapshots; ctx only
+ * names the device and its launch knobs ("blocks_per_cu", "classes_hash_bits"). It enqueues on
+ * hip_stream and synchronises it once per pass: the signatures (8 bytes per end point) and the marks
+ * of the equality check come back to the host, which picks the candidates; the matrix is read on the
+ * device only. n_svc, n_src or n_dst zero: PG_OK, *result zeroed, nothing else written (the matrix
+ * may then be null). PG_EINVAL (pg_last_error says which): a null spec, matrix or result; both class
+ * outputs null; out_quotient with a class output missing; a side above 2^20; n_svc above 4096; n_svc
+ * * n_src * row_words >= 2^32. PG_ENOMEM: the scratch allocation (signatures, leaders, marks) failed. */
+typedef struct pg_reach_classes_spec {
+    const uint32_t* matrix;   /* device: a pg_reach_matrix out_packed, n_svc * n_src rows of pg_reach_row_words(n_dst) words */
+    uint32_t n_svc, n_src, n_dst;
+} pg_reach_classes_spec;
+typedef struct pg_reach_classes_result {   /* host */
+    uint32_t n_src_classes;   /* 0 for a side that was not asked for */
+    uint32_t n_dst_classes;
+    uint32_t rounds;          /* the most passes of the equality check either side needed: 1 unless different
+                                 signatures shared a hash; 0 on empty input */
+} pg_reach_classes_result;
+int pg_reach_classes(pg_ctx* ctx, const pg_reach_classes_spec* spec, uint32_t* out_src_class, uint32_t* out_dst_class,
+                     uint32_t* out_src_rep, uint32_t* out_dst_rep, uint32_t* out_quotient,
+                     pg_reach_classes_result* result, void* hip_stream);
+/* TESTS ONLY -- never on the audit path: pg_reach_classes's per-word code, signatures, rounds and plan
+ * (classes.hpp, the functions the kernels and the launch call) on the host, work item by work item;
+ * matrix and every output are host arrays. Does not touch the device. */
+int pg_debug_reach_classes_host(pg_ctx* ctx, const pg_reach_classes_spec* spec, uint32_t* out_src_class,
+                                uint32_t* out_dst_class, uint32_t* out_src_rep, uint32_t* out_dst_rep,
+                                uint32_t* out_quotient, pg_reach_classes_result* result);
+/* TESTS ONLY: how the column passes of a pg_reach_classes over rows of n_dst cells are cut, from the
+ * one function the launch itself uses (classes.hpp classes_plan): the column words of a work item's
+ * tile, and the rows (of the n_svc * n_src) of a chunk of the dst signatures and of the dst check.
+ * Launches nothing. */
+int pg_debug_reach_classes_plan(pg_ctx* ctx, uint32_t n_dst, uint32_t* tile_words, uint32_t* chunk_rows,
+                                uint32_t* check_rows);
 
 /* ---- policy configurator ------------------------------------------
  * configurator.PolicyConfiguratorAPI / Txn (plugins/policy/configurator/configurator_api.go:28-54,

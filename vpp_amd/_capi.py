@@ -131,6 +131,14 @@ class pg_reach_paths_result(C.Structure):
                 ("n_broken", C.c_uint64), ("n_via", C.c_uint64), ("longest", C.c_uint32)]
 
 
+class pg_reach_classes_spec(C.Structure):
+    _fields_ = [("matrix", C.c_void_p), ("n_svc", C.c_uint32), ("n_src", C.c_uint32), ("n_dst", C.c_uint32)]
+
+
+class pg_reach_classes_result(C.Structure):
+    _fields_ = [("n_src_classes", C.c_uint32), ("n_dst_classes", C.c_uint32), ("rounds", C.c_uint32)]
+
+
 class pg_pod_id(C.Structure):
     _fields_ = [("ns", C.c_char_p), ("name", C.c_char_p)]
 
@@ -296,6 +304,12 @@ _SIGS = {
     "pg_debug_reach_paths_host": (C.c_int, [_P, C.POINTER(pg_reach_paths_spec), _P, _P, _P,
                                             C.POINTER(pg_reach_paths_result)]),
     "pg_debug_reach_paths_plan": (C.c_int, [_P, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "pg_reach_classes": (C.c_int, [_P, C.POINTER(pg_reach_classes_spec), _P, _P, _P, _P, _P,
+                                   C.POINTER(pg_reach_classes_result), _P]),
+    "pg_debug_reach_classes_host": (C.c_int, [_P, C.POINTER(pg_reach_classes_spec), _P, _P, _P, _P, _P,
+                                              C.POINTER(pg_reach_classes_result)]),
+    "pg_debug_reach_classes_plan": (C.c_int, [_P, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                              C.POINTER(C.c_uint32)]),
     "pg_session_rules_new": (_P, [C.c_char_p]),
     "pg_session_rules_free": (None, [_P]),
     "pg_session_rules_clear": (C.c_int, [_P]),

@@ -1,10 +1,11 @@
 // extern "C" boundary of the reachability audits (include/policygpu.h): the matrix, the port sweep,
-// the diff, the closure, the groups and the paths, each with the host twin the tests compare its
-// kernels to.
+// the diff, the closure, the groups, the paths and the classes, each with the host twin the tests
+// compare its kernels to.
 #include <algorithm>
 #include <numeric>
 
 #include "capi_internal.hpp"
+#include "classes.hpp"
 #include "closure.hpp"
 #include "diff.hpp"
 #include "groups.hpp"
@@ -718,6 +719,165 @@ int pg_debug_reach_paths_plan(pg_ctx* ctx, uint32_t n, uint32_t* chunk_queries, 
     if (!ctx || !chunk_queries || !lds_bytes) return PG_EINVAL;
     const PathsPlan p = paths_plan(n);
     *chunk_queries = p.chunk_queries, *lds_bytes = p.lds_bytes;
+    return PG_OK;
+}
+
+}  // extern "C"
+
+// ---- reachability classes (classes.hpp) ----------------------------------------------------------
+namespace {
+static_assert(sizeof(pg_reach_classes_result) == sizeof(ClassesResult), "pg_reach_classes_result is classes.hpp's ClassesResult");
+
+// argument checks shared by pg_reach_classes and its host twin: PG_OK with *result zeroed, and *empty
+// set when there is nothing to do
+int classes_args(pg_ctx* ctx, const pg_reach_classes_spec* spec, const uint32_t* out_src_class, const uint32_t* out_dst_class,
+                 const uint32_t* out_quotient, pg_reach_classes_result* result, bool* empty) {
+    if (!ctx) return PG_EINVAL;
+    if (!spec || !result) return fail(ctx, PG_EINVAL, "null spec or result");
+    if (!out_src_class && !out_dst_class) return fail(ctx, PG_EINVAL, "out_src_class and out_dst_class are both null");
+    if (out_quotient && (!out_src_class || !out_dst_class))
+        return fail(ctx, PG_EINVAL, "out_quotient needs out_src_class and out_dst_class");
+    if (spec->n_src > kClassesMaxSide || spec->n_dst > kClassesMaxSide) return fail(ctx, PG_EINVAL, "a side longer than 2^20");
+    if (spec->n_svc > kClassesMaxSvc) return fail(ctx, PG_EINVAL, "more than 4096 services");
+    *empty = !spec->n_svc || !spec->n_src || !spec->n_dst;
+    if (!*empty) {
+        if (!spec->matrix) return fail(ctx, PG_EINVAL, "null matrix");
+        if ((uint64_t)spec->n_svc * spec->n_src * reach_row_words(spec->n_dst) >> 32)
+            return fail(ctx, PG_EINVAL, "n_svc * n_src * row_words reaches 2^32");
+    }
+    *result = pg_reach_classes_result{0, 0, 0};
+    return PG_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int pg_reach_classes(pg_ctx* ctx, const pg_reach_classes_spec* spec, uint32_t* out_src_class, uint32_t* out_dst_class,
+                     uint32_t* out_src_rep, uint32_t* out_dst_rep, uint32_t* out_quotient, pg_reach_classes_result* result,
+                     void* stream) {
+    GUARD_BEGIN
+    bool empty = false;
+    if (int rc = classes_args(ctx, spec, out_src_class, out_dst_class, out_quotient, result, &empty)) return rc;
+    if (empty) return PG_OK;
+    DEVICE_GUARD(ctx);
+    const ClassesSpecDev sd{spec->matrix, spec->n_svc, spec->n_src, spec->n_dst, ctx->eng.tune.classes_hash_bits};
+    const ClassesOutDev od{out_src_class, out_dst_class, out_src_rep, out_dst_rep, out_quotient};
+    std::string err;
+    ClassesResult r{0, 0, 0};
+    const int rc = dev_reach_classes(ctx->eng.tune.blocks_per_cu, sd, od, &r, stream, &err);
+    if (rc != 0) return fail(ctx, rc == -2 ? PG_ENOMEM : PG_EIO, err);
+    *result = pg_reach_classes_result{r.n_src_classes, r.n_dst_classes, r.rounds};
+    return PG_OK;
+    GUARD_END(ctx)
+}
+
+int pg_debug_reach_classes_host(pg_ctx* ctx, const pg_reach_classes_spec* spec, uint32_t* out_src_class,
+                                uint32_t* out_dst_class, uint32_t* out_src_rep, uint32_t* out_dst_rep, uint32_t* out_quotient,
+                                pg_reach_classes_result* result) {
+    GUARD_BEGIN
+    bool empty = false;
+    if (int rc = classes_args(ctx, spec, out_src_class, out_dst_class, out_quotient, result, &empty)) return rc;
+    if (empty) return PG_OK;
+    const uint32_t n_svc = spec->n_svc, n_src = spec->n_src, n_dst = spec->n_dst, rw = (uint32_t)reach_row_words(n_dst);
+    const uint32_t n_rows = n_svc * n_src, bits = ctx->eng.tune.classes_hash_bits;
+    const uint32_t* m = spec->matrix;
+    const ClassesPlan plan = classes_plan(n_dst);
+    const uint32_t tiles = (rw + plan.tile_words - 1u) / plan.tile_words, phases = kClassesBlock / plan.tile_words;
+    // every work item (chunk of chunk_rows rows, tile) of a column kernel in order, its lanes as they
+    // run: lane(w, first row, end of the chunk)
+    auto column_items = [&](uint32_t chunk_rows, auto&& lane) {
+        const uint32_t n_chunks = (n_rows + chunk_rows - 1u) / chunk_rows;
+        for (uint32_t ch = 0; ch < n_chunks; ch++)
+            for (uint32_t tile = 0; tile < tiles; tile++)
+                for (uint32_t t = 0; t < kClassesBlock; t++) {
+                    const uint32_t w = tile * plan.tile_words + t % plan.tile_words;
+                    const uint64_t r0 = (uint64_t)ch * chunk_rows + t / plan.tile_words;
+                    const uint64_t r1 = std::min<uint64_t>((uint64_t)(ch + 1u) * chunk_rows, n_rows);
+                    if (w < rw && r0 < r1) lane(w, r0, r1);
+                }
+    };
+    ClassesSide src, dst;
+    std::vector<uint64_t> sig;
+    if (out_src_class) {
+        // as k_classes_hash_src: a wave per end point, its lanes' terms summed
+        sig.assign(n_src, 0);
+        for (uint32_t i = 0; i < n_src; i++)
+            for (uint32_t lane = 0; lane < kClassesWave; lane++)
+                for (uint32_t v = 0; v < n_svc; v++)
+                    for (uint32_t w = lane; w < rw; w += kClassesWave)
+                        sig[i] += classes_src_term(m[((uint64_t)v * n_src + i) * rw + w] & 3u * diff_valid(n_dst, w), w, v);
+        // as k_classes_check_src: a wave per pair
+        auto check = [&](const std::vector<uint32_t>& pending, const std::vector<uint32_t>& leader, std::vector<uint8_t>& differs) {
+            for (size_t k = 0; k < pending.size(); k++) {
+                const uint32_t a = pending[k], b = leader[a];
+                uint32_t bad = 0;
+                for (uint32_t v = 0; v < n_svc; v++)
+                    for (uint32_t w = 0; w < rw; w++)
+                        bad |= (m[((uint64_t)v * n_src + a) * rw + w] ^ m[((uint64_t)v * n_src + b) * rw + w]) & 3u * diff_valid(n_dst, w);
+                differs[k] = bad != 0;
+            }
+            return 0;
+        };
+        classes_resolve(sig.data(), n_src, bits, check, &src);
+    }
+    if (out_dst_class) {
+        // as k_classes_hash_dst
+        sig.assign(16u * (size_t)rw, 0);
+        column_items(plan.chunk_rows, [&](uint32_t w, uint64_t r0, uint64_t r1) {
+            const uint32_t mask = 3u * diff_valid(n_dst, w);
+            ClassesAcc a = {};
+            for (uint64_t r = r0; r < r1; r += phases) classes_dst_add(a, m[r * rw + w] & mask, classes_row_key(r));
+            for (uint32_t k = 0; k < 16; k++) sig[16u * (size_t)w + k] += a.h[k];
+        });
+        // as k_classes_check_dst
+        std::vector<uint32_t> lead(16u * (size_t)rw), marks(16u * (size_t)rw);
+        auto check = [&](const std::vector<uint32_t>& pending, const std::vector<uint32_t>& leader, std::vector<uint8_t>& differs) {
+            for (uint32_t j = 0; j < 16u * rw; j++) lead[j] = j, marks[j] = 0;
+            for (uint32_t j : pending) lead[j] = leader[j];
+            column_items(plan.check_rows, [&](uint32_t w, uint64_t r0, uint64_t r1) {
+                uint32_t ld[16];
+                for (uint32_t k = 0; k < 16; k++) ld[k] = lead[16u * (size_t)w + k];
+                if (!classes_dst_pending(ld, w)) return;
+                uint32_t bad = 0;
+                for (uint64_t r = r0; r < r1; r += phases) {
+                    const uint32_t* row = m + r * rw;
+                    bad |= classes_dst_differs(row[w], ld, w, [&](uint32_t lw) { return row[lw]; });
+                }
+                for (uint32_t k = 0; k < 16; k++)
+                    if (bad >> k & 1u) marks[16u * (size_t)w + k] = 1u;
+            });
+            for (size_t k = 0; k < pending.size(); k++) differs[k] = marks[pending[k]] != 0;
+            return 0;
+        };
+        classes_resolve(sig.data(), n_dst, bits, check, &dst);
+    }
+    if (out_src_class) std::copy(src.cls.begin(), src.cls.end(), out_src_class);
+    if (out_src_class && out_src_rep) std::copy(src.rep.begin(), src.rep.end(), out_src_rep);
+    if (out_dst_class) std::copy(dst.cls.begin(), dst.cls.end(), out_dst_class);
+    if (out_dst_class && out_dst_rep) std::copy(dst.rep.begin(), dst.rep.end(), out_dst_rep);
+    const uint32_t n_sc = (uint32_t)src.rep.size(), n_dc = (uint32_t)dst.rep.size();
+    if (out_quotient) {  // as k_classes_quotient
+        const uint32_t rwq = (uint32_t)reach_row_words(n_dc);
+        for (uint32_t v = 0; v < n_svc; v++)
+            for (uint32_t cs = 0; cs < n_sc; cs++)
+                for (uint32_t jw = 0; jw < rwq; jw++) {
+                    const uint32_t left = std::min(16u, n_dc - 16u * jw);
+                    uint32_t rep[16] = {};
+                    std::copy_n(dst.rep.begin() + 16u * jw, left, rep);
+                    out_quotient[((size_t)v * n_sc + cs) * rwq + jw] =
+                        classes_quotient_word(m + ((uint64_t)v * n_src + src.rep[cs]) * rw, rep, left);
+                }
+    }
+    *result = pg_reach_classes_result{n_sc, n_dc, std::max(src.rounds, dst.rounds)};
+    return PG_OK;
+    GUARD_END(ctx)
+}
+
+int pg_debug_reach_classes_plan(pg_ctx* ctx, uint32_t n_dst, uint32_t* tile_words, uint32_t* chunk_rows,
+                                uint32_t* check_rows) {
+    if (!ctx || !tile_words || !chunk_rows || !check_rows) return PG_EINVAL;
+    const ClassesPlan p = classes_plan(n_dst);
+    *tile_words = p.tile_words, *chunk_rows = p.chunk_rows, *check_rows = p.check_rows;
     return PG_OK;
 }
 

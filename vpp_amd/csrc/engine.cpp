@@ -70,6 +70,7 @@ const Knob kKnobs[] = {
     {"block_stage", &Tuning::block_stage, 0, 1024, false},
     {"hist_window", &Tuning::hist_window, 1, 16382, false},
     {"launch_max_tuples", &Tuning::launch_max_tuples, 0, (1 << 30) - 64, false},
+    {"classes_hash_bits", &Tuning::classes_hash_bits, 0, 64, false},
 };
 bool Knob::allowed(int v) const {
     if (field == &Tuning::lc_max_stride) return v == 12 || v == 16 || v == 18;

@@ -505,6 +505,46 @@ def unpack_paths(lengths, nodes):
             for q in range(d.size)]
 
 
+# ---- reachability classes (include/policygpu.h pg_reach_classes) -----------------------------
+def classes_result(res):
+    return {"n_src_classes": res.n_src_classes, "n_dst_classes": res.n_dst_classes, "rounds": res.rounds}
+
+
+def reach_classes(engine, matrix, n_svc, n_src, n_dst, src=True, dst=True, reps=False, quotient=False, stream=None):
+    """The end points of a reach_matrix result that the policy treats identically, on the GPU
+    (pg_reach_classes). ``matrix`` is an int32 device tensor [n_svc, n_src, row_words(n_dst)]; ``src`` /
+    ``dst`` say which sides are classed. -> (src_class, dst_class, src_rep, dst_rep, quotient, result):
+    the class of every end point as int32 tensors [n_src] / [n_dst], numbered by first appearance; with
+    ``reps`` each class's least member as int32 tensors [n_src_classes] / [n_dst_classes]; with
+    ``quotient`` (both sides) the matrix of the representatives as an int32 tensor [n_svc,
+    n_src_classes, row_words(n_dst_classes)] in the audits' layout (unpack_reach, reach_diff,
+    reach_groups); and {n_src_classes, n_dst_classes, rounds}. Whatever was not asked for is None. The
+    call never touches the hit counters."""
+    rw = reach_row_words(n_dst)
+    if matrix.dtype != torch.int32 or not matrix.is_contiguous() or matrix.numel() != n_svc * n_src * rw:
+        raise ValueError("a contiguous int32 tensor [n_svc, n_src, row_words(n_dst)] expected")
+    if not (src or dst) or (quotient and not (src and dst)):
+        raise ValueError("at least one side, and both for the quotient")
+    new = lambda n: torch.empty(n, dtype=torch.int32, device="cuda")
+    sc, dc = new(n_src) if src else None, new(n_dst) if dst else None
+    sr, dr = new(n_src) if src and reps else None, new(n_dst) if dst and reps else None
+    q = new(matrix.numel()) if quotient else None
+    res = _capi.pg_reach_classes_result()
+    if matrix.numel():  # (an empty tensor has no address to hand over; the call would write nothing)
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+        engine._ck(lib.pg_reach_classes(engine.h, C.byref(_capi.pg_reach_classes_spec(matrix.data_ptr(), int(n_svc), int(n_src),
+                                                                                      int(n_dst))),
+                                        ptr(sc), ptr(dc), ptr(sr), ptr(dr), ptr(q), C.byref(res), _stream_ptr(stream)))
+    n_sc, n_dc = res.n_src_classes, res.n_dst_classes
+    if sr is not None:
+        sr = sr[:n_sc]
+    if dr is not None:
+        dr = dr[:n_dc]
+    if q is not None:
+        q = q[:n_svc * n_sc * reach_row_words(n_dc)].reshape(n_svc, n_sc, reach_row_words(n_dc))
+    return sc, dc, sr, dr, q, classes_result(res)
+
+
 def unpack(out_u32):
     w = out_u32.astype(np.uint32)
     return (w >> 30).astype(np.int64), (w & 0x3FFFFFFF).astype(np.int64)

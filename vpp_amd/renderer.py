@@ -700,6 +700,64 @@ class Engine:
         sn, dn = list(src_groups), list(dst_groups)
         return [(int(r) // n_sg, sn[int(r) % n_sg], dn[int(j)], int(x), int(y)) for r, j, x, y in zip(row, col, cb, ca)]
 
+    def debug_reach_classes_host(self, matrix, n_svc, n_src, n_dst, src=True, dst=True, reps=True, quotient=True):
+        """TESTS ONLY: pg_reach_classes's per-word code, signatures, rounds and plan run on the host
+        (pg_debug_reach_classes_host) over a numpy array of packed words [n_svc, n_src,
+        row_words(n_dst)]. -> (src_class u32 [n_src], dst_class u32 [n_dst], src_rep u32 [n_src_classes],
+        dst_rep u32 [n_dst_classes], quotient words u32 [n_svc, n_src_classes, row_words(n_dst_classes)],
+        {n_src_classes, n_dst_classes, rounds}), None for what was not asked for."""
+        import numpy as np
+        from . import device as D
+        m = np.ascontiguousarray(matrix, dtype=np.uint32)
+        quotient = quotient and src and dst
+        new = lambda n: np.full(n, 0xFFFFFFFF, np.uint32)
+        sc, dc = new(n_src) if src else None, new(n_dst) if dst else None
+        sr, dr = new(n_src) if src and reps else None, new(n_dst) if dst and reps else None
+        q = new(m.size) if quotient else None
+        res = _capi.pg_reach_classes_result()
+        if m.size:
+            p = lambda x: x.ctypes.data_as(C.c_void_p) if x is not None and x.size else None
+            spec = _capi.pg_reach_classes_spec(m.ctypes.data, int(n_svc), int(n_src), int(n_dst))
+            self._ck(lib.pg_debug_reach_classes_host(self.h, C.byref(spec), p(sc), p(dc), p(sr), p(dr), p(q), C.byref(res)))
+        n_sc, n_dc = res.n_src_classes, res.n_dst_classes
+        rwq = lib.pg_reach_row_words(n_dc)
+        return (sc, dc, None if sr is None else sr[:n_sc], None if dr is None else dr[:n_dc],
+                None if q is None else q[:n_svc * n_sc * rwq].reshape(n_svc, n_sc, rwq), D.classes_result(res))
+
+    def debug_reach_classes_plan(self, n_dst):
+        """TESTS ONLY: how the column passes of pg_reach_classes cut rows of n_dst cells
+        (pg_debug_reach_classes_plan) -> {tile_words, chunk_rows, check_rows}"""
+        t, c, k = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        self._ck(lib.pg_debug_reach_classes_plan(self.h, int(n_dst), C.byref(t), C.byref(c), C.byref(k)))
+        return {"tile_words": t.value, "chunk_rows": c.value, "check_rows": k.value}
+
+    def reachability_classes(self, src_pods, dst_pods, services, host=False):
+        """Which pods the policy treats as one role: the src pods with identical rows and the dst pods
+        with identical columns over all of ``services``, by one pg_reach_matrix and one
+        pg_reach_classes. -> (src classes, dst classes, codes): two lists of pod lists, the classes in
+        the order of their first member and every class's members in list order (a pod listed twice
+        is there twice), and the ConnActions uint8 [n_svc, n_src_classes, n_dst_classes] of the
+        classes' first members. Pods and services as in reachability. ``host``: TESTS ONLY, the host
+        twins."""
+        import numpy as np
+        from . import device as D
+        src, dst = self._pod_ips(src_pods), self._pod_ips(dst_pods)
+        n_svc, n_src, n_dst = len(services), len(src), len(dst)
+        if not n_svc or not n_src or not n_dst:
+            # (no cell tells two end points apart: each side is one class)
+            one = lambda pods: [list(pods)] if len(pods) else []
+            return one(src_pods), one(dst_pods), np.zeros((n_svc, min(n_src, 1), min(n_dst, 1)), np.uint8)
+        if host:
+            m = self.debug_reach_matrix_host(src, dst, services, words=False)
+            sc, dc, _, _, q, res = self.debug_reach_classes_host(m, n_svc, n_src, n_dst, reps=False)
+        else:
+            m = D.reach_matrix(self, src, dst, services)
+            sc, dc, _, _, q, res = D.reach_classes(self, m, n_svc, n_src, n_dst, quotient=True)
+            sc, dc = sc.cpu().numpy(), dc.cpu().numpy()
+        n_sc, n_dc = res["n_src_classes"], res["n_dst_classes"]
+        members = lambda cls, pods, n: [[pods[k] for k in np.flatnonzero(cls == c)] for c in range(n)]
+        return members(sc, src_pods, n_sc), members(dc, dst_pods, n_dc), D.unpack_reach(q, n_svc, n_sc, n_dc)
+
     def debug_walk_stats(self, table_id, src, dst, dport, proto):
         """MEASUREMENT: per tuple, the loads a SINGLE launch on table_id makes of the table's
         structure (pg_debug_walk_stats) -> (lds_reads u32[n], mem_reads u32[n], launch STAGE)"""
