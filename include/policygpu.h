@@ -188,7 +188,13 @@ int pg_ctx_device(const pg_ctx* ctx);
  * the largest a launch's 32-bit stream offsets allow, 2^30 - 64; default 0), "classes_hash_bits"
  * (pg_reach_classes keeps only this many low bits of every signature, 0..64, 0 = every signature
  * equal; the result does not depend on it, only the rounds of the equality check do -- for tests
- * that reach those rounds at small shapes; default 64).
+ * that reach those rounds at small shapes; default 64), "rules_hist_cells" (pg_reach_rules: cap of
+ * the u32 LDS cells a workgroup counts into before its global atomics, both histograms together,
+ * 0..16384; what does not fit is counted with global atomics, 0 = global atomics only; the result
+ * does not depend on it -- for tests that reach the global path at small shapes; default 16384 =
+ * whatever fits), "rules_wave_agg" (pg_reach_rules: 1/0, the lanes of a wave that hit the first
+ * active lane's cell add with one atomic instead of one each; the result does not depend on it;
+ * default 1, DESIGN.md has the measurement).
  * pg_ctx_set_tuning sets one context's knob; pg_set_tuning sets the process default that
  * contexts created afterwards start from. PG_EINVAL for an unknown key or a value out of range. */
 int pg_ctx_set_tuning(pg_ctx* ctx, const char* key, int value);
@@ -833,6 +839,82 @@ int pg_debug_reach_classes_host(pg_ctx* ctx, const pg_reach_classes_spec* spec, 
  * Launches nothing. */
 int pg_debug_reach_classes_plan(pg_ctx* ctx, uint32_t n_dst, uint32_t* tile_words, uint32_t* chunk_rows,
                                 uint32_t* check_rows);
+
+/* ---- rule coverage: per-rule histograms of a reach product, on the device --------------------
+ * "Which rules do any work over my inventory, which are dead or shadowed, and which rule denies the
+ * most pairs?" The product is pg_reach_matrix's (the pg_reach_spec fields: the same end-point
+ * resolution, preamble FAILUREs and form A / form B partition of the services), but no cell is
+ * written: the call counts, per counter slot (pg_num_counter_slots, pg_slot_info),
+ *   out_evals  device, optional, n_slots u64: out_evals[s] = the weighted number of evalACL
+ *              evaluations over the product that slot s decided; one count at the "unresolved" slot
+ *              per pair that fails the preamble, evaluations of an interface without an ACL at the
+ *              "no ACL" slot. Exactly what pg_classify(PG_MODE_CONN, counters) adds to a zeroed
+ *              counter array for the product's tuples, each tuple of slice v repeated svc_weight[v]
+ *              times
+ *   out_cells  device, optional, 4 * n_slots u64: out_cells[4 * s + c] = the weighted number of
+ *              cells (v, i, j) whose verdict word is c << 30 | s -- the histogram of pg_reach_matrix's
+ *              out_words without writing them. It sums to n_src * n_dst * (the sum of the weights)
+ * At least one of the two is given. The call clears them on hip_stream before it adds, so every
+ * entry is written, zeros included. Both are integer sums: exact, and the same on every run.
+ *   svc_weight host, optional, n_svc: cell and evaluations of slice v count svc_weight[v] times, 0 ..
+ *              65536; NULL = every weight 1; 0 = the slice contributes nothing. With the services the
+ *              representatives lo[k] of pg_port_intervals and the weights the interval lengths, one
+ *              call covers all 65,536 dst ports of a protocol exactly at K evaluations per pair
+ *   n_slots    the slot count the caller sized out_evals / out_cells for
+ *   result     host, required: n_slots and the layout generation the counts are in
+ *              (pg_counter_layout_gen), n_cells = n_src * n_dst * sum of weights, n_evals = the sum of
+ *              out_evals, n_rule_slots = the slots whose pg_slot_info rule index is >= 0,
+ *              n_dead_rules = those of them with out_evals == 0 (0 when out_evals is not given)
+ * The call is an audit, not traffic: it never touches the hit counters or their snapshots. Like
+ * pg_reach_matrix it compiles and uploads stale tables first; it enqueues on hip_stream and
+ * synchronises it, because the result comes back to the host. A zero n_src, n_dst or n_svc: PG_OK,
+ * the given outputs cleared, *result zeroed apart from n_slots and layout_gen. PG_EINVAL
+ * (pg_last_error says which): a null spec or result; both outputs null; a side above 2^20; more than
+ * 4096 services; a weight above 65536; n_slots different from the current pg_num_counter_slots (the
+ * ACLs changed since the caller sized its arrays); n_src * n_dst * sum of weights * 4 >= 2^63. */
+typedef struct pg_reach_rules_spec {
+    const uint32_t* src_ip;   /* the pg_reach_spec fields */
+    size_t n_src;
+    const uint32_t* dst_ip;
+    size_t n_dst;
+    const pg_service* services;
+    size_t n_svc;
+    const uint32_t* svc_weight; /* host, n_svc, or NULL */
+    size_t n_slots;
+} pg_reach_rules_spec;
+typedef struct pg_reach_rules_result {   /* host */
+    uint64_t layout_gen;
+    uint64_t n_cells;
+    uint64_t n_evals;
+    uint32_t n_slots;
+    uint32_t n_rule_slots;
+    uint32_t n_dead_rules;
+} pg_reach_rules_result;
+int pg_reach_rules(pg_ctx* ctx, const pg_reach_rules_spec* spec, uint64_t* out_evals, uint64_t* out_cells,
+                   pg_reach_rules_result* result, void* hip_stream);
+/* TESTS ONLY -- never on the audit path: pg_reach_rules's per-word code, sink, windows and flushes
+ * (rules.hpp, the templates the kernel instantiates and the plan the launch uses) run on the host,
+ * work item by work item, with host output arrays. flags as in pg_debug_reach_matrix_host.
+ * PG_EFAULT if a 32-bit window cell wrapped (the plan's flush bound rules that out). Does not touch
+ * the device. */
+int pg_debug_reach_rules_host(pg_ctx* ctx, const pg_reach_rules_spec* spec, uint64_t* out_evals, uint64_t* out_cells,
+                              pg_reach_rules_result* result, int flags);
+/* TESTS ONLY: the launch plan of a pg_reach_rules over n_slots slots, the last n_tail of them past
+ * the rules, with the given outputs and a largest weight of max_weight under this context's
+ * "rules_hist_cells", from the one function the launch itself uses (rules.hpp rules_plan): the
+ * workgroup size; per histogram the LDS cells and the first index of its window (the window wraps
+ * from the last index to index 0; cells_* in units of one 4 * s + c index); the words a workgroup may
+ * process between two flushes; the LDS bytes. *resident (optional; needs the device) = the
+ * workgroups the device holds at once under "blocks_per_cu". Launches nothing. */
+typedef struct pg_reach_rules_plan {
+    uint32_t block;
+    uint32_t evals_cells, evals_base;
+    uint32_t cells_cells, cells_base;
+    uint32_t flush_words;
+    uint32_t lds_bytes;
+} pg_reach_rules_plan;
+int pg_debug_reach_rules_plan(pg_ctx* ctx, uint32_t n_slots, uint32_t n_tail, int evals, int cells, uint32_t max_weight,
+                              pg_reach_rules_plan* plan, uint32_t* resident);
 
 /* ---- policy configurator ------------------------------------------
  * configurator.PolicyConfiguratorAPI / Txn (plugins/policy/configurator/configurator_api.go:28-54,

@@ -115,7 +115,7 @@ def main():
         "tool": "reach_bench", "engine": "config-5 cluster (workloads.cluster_engine)",
         "n_src": ns, "n_dst": nd, "n_svc": n_svc, "pairs": pairs, "reps": a.reps,
         "verdict_mix": np.bincount(acts.ravel(), minlength=4).tolist(),
-        "matrix_ms_best": min(t_mat), "matrix_ms_median": statistics.median(t_mat),
+        "matrix_ms_best": min(t_mat), "matrix_ms_median": statistics.median(t_mat), "matrix_ms_all": t_mat,
         "matrix_words_ms_best": min(t_words),
         "classify_ms_best": min(t_cls), "classify_ms_median": statistics.median(t_cls),
         "classify_plus_materialise_ms_best": min(t_mz),

@@ -139,6 +139,23 @@ class pg_reach_classes_result(C.Structure):
     _fields_ = [("n_src_classes", C.c_uint32), ("n_dst_classes", C.c_uint32), ("rounds", C.c_uint32)]
 
 
+class pg_reach_rules_spec(C.Structure):
+    _fields_ = [("src_ip", C.c_void_p), ("n_src", C.c_size_t), ("dst_ip", C.c_void_p), ("n_dst", C.c_size_t),
+                ("services", C.POINTER(pg_service)), ("n_svc", C.c_size_t), ("svc_weight", C.c_void_p),
+                ("n_slots", C.c_size_t)]
+
+
+class pg_reach_rules_result(C.Structure):
+    _fields_ = [("layout_gen", C.c_uint64), ("n_cells", C.c_uint64), ("n_evals", C.c_uint64), ("n_slots", C.c_uint32),
+                ("n_rule_slots", C.c_uint32), ("n_dead_rules", C.c_uint32)]
+
+
+class pg_reach_rules_plan(C.Structure):
+    _fields_ = [("block", C.c_uint32), ("evals_cells", C.c_uint32), ("evals_base", C.c_uint32),
+                ("cells_cells", C.c_uint32), ("cells_base", C.c_uint32), ("flush_words", C.c_uint32),
+                ("lds_bytes", C.c_uint32)]
+
+
 class pg_pod_id(C.Structure):
     _fields_ = [("ns", C.c_char_p), ("name", C.c_char_p)]
 
@@ -310,6 +327,11 @@ _SIGS = {
                                               C.POINTER(pg_reach_classes_result)]),
     "pg_debug_reach_classes_plan": (C.c_int, [_P, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                               C.POINTER(C.c_uint32)]),
+    "pg_reach_rules": (C.c_int, [_P, C.POINTER(pg_reach_rules_spec), _P, _P, C.POINTER(pg_reach_rules_result), _P]),
+    "pg_debug_reach_rules_host": (C.c_int, [_P, C.POINTER(pg_reach_rules_spec), _P, _P,
+                                            C.POINTER(pg_reach_rules_result), C.c_int]),
+    "pg_debug_reach_rules_plan": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_uint32,
+                                            C.POINTER(pg_reach_rules_plan), C.POINTER(C.c_uint32)]),
     "pg_session_rules_new": (_P, [C.c_char_p]),
     "pg_session_rules_free": (None, [_P]),
     "pg_session_rules_clear": (C.c_int, [_P]),

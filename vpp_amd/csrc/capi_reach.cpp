@@ -1,6 +1,6 @@
-// extern "C" boundary of the reachability audits (include/policygpu.h): the matrix, the port sweep,
-// the diff, the closure, the groups, the paths and the classes, each with the host twin the tests
-// compare its kernels to.
+// extern "C" boundary of the reachability audits (include/policygpu.h): the matrix, the rule
+// coverage, the port sweep, the diff, the closure, the groups, the paths and the classes, each with
+// the host twin the tests compare its kernels to.
 #include <algorithm>
 #include <numeric>
 
@@ -11,6 +11,7 @@
 #include "groups.hpp"
 #include "paths.hpp"
 #include "ports.hpp"
+#include "rules.hpp"
 
 using namespace pg;
 
@@ -136,6 +137,197 @@ int pg_debug_reach_matrix_host(pg_ctx* ctx, const pg_reach_spec* spec, uint32_t*
         const ReachEnds ends = H.run(false, T, *spec, svc, lb);
         const ReachPass P{ends, H.g.data(), lb.data(), (uint32_t)lb.size(), out_packed, out_words};
         host_reach_pairs<false, false>(T, P);
+    }
+    return PG_OK;
+    GUARD_END(ctx)
+}
+
+}  // extern "C"
+
+// ---- rule coverage (rules.hpp) -------------------------------------------------------------------
+namespace {
+static_assert(sizeof(pg_reach_rules_plan) == 7 * sizeof(uint32_t), "pg_reach_rules_plan is seven words");
+
+// what pg_reach_rules and its host twin work on once the arguments are checked
+struct RulesCall {
+    pg_reach_spec reach;           // the spec's pg_reach_spec fields
+    std::vector<W4> svc;
+    std::vector<uint32_t> weight;  // per service (1 where svc_weight is null)
+    uint32_t n_slots = 0, n_rule_slots = 0, max_weight = 0;
+    bool empty = false;
+};
+
+// Argument checks shared by pg_reach_rules and its host twin (inside a GUARD: the compile may
+// throw). PG_OK: *c filled, *result = {layout_gen, n_cells, 0, n_slots, n_rule_slots, 0} (zeroed
+// apart from n_slots and layout_gen when c->empty)
+int rules_args(pg_ctx* ctx, const pg_reach_rules_spec* spec, const uint64_t* out_evals, const uint64_t* out_cells,
+               pg_reach_rules_result* result, RulesCall* c) {
+    if (!ctx) return PG_EINVAL;
+    if (!spec || !result) return fail(ctx, PG_EINVAL, "null spec or result");
+    if (!out_evals && !out_cells) return fail(ctx, PG_EINVAL, "out_evals and out_cells are both null");
+    if (spec->n_src > kReachMaxSide || spec->n_dst > kReachMaxSide) return fail(ctx, PG_EINVAL, "a side longer than 2^20");
+    if (spec->n_svc > kReachMaxSvc) return fail(ctx, PG_EINVAL, "more than 4096 services");
+    c->empty = !spec->n_src || !spec->n_dst || !spec->n_svc;
+    if (!c->empty && (!spec->src_ip || !spec->dst_ip || !spec->services)) return fail(ctx, PG_EINVAL, "null spec array");
+    c->reach = pg_reach_spec{spec->src_ip, spec->n_src, spec->dst_ip, spec->n_dst, spec->services, spec->n_svc};
+    uint64_t sum = 0;
+    c->weight.assign(spec->n_svc, 1u);
+    for (size_t v = 0; v < spec->n_svc; v++) {
+        if (spec->svc_weight) c->weight[v] = spec->svc_weight[v];
+        if (c->weight[v] > kRulesMaxWeight)
+            return fail(ctx, PG_EINVAL, "svc_weight[" + std::to_string(v) + "] = " + std::to_string(c->weight[v]) + " is above 65536");
+        sum += c->weight[v];
+        c->max_weight = std::max(c->max_weight, c->weight[v]);
+    }
+    Engine& E = ctx->eng;
+    if (!E.compiled) E.compile();
+    c->n_slots = (uint32_t)E.slot_table.size();
+    if (spec->n_slots != c->n_slots)
+        return fail(ctx, PG_EINVAL, "n_slots is " + std::to_string(spec->n_slots) + " but the installed ACLs give " +
+                                        std::to_string(c->n_slots) + " counter slots: they changed since pg_num_counter_slots");
+    // (both sides <= 2^20 and the weights add to at most 2^28: the product fits 64 bits only after this check)
+    const uint64_t pairs = (uint64_t)spec->n_src * spec->n_dst;
+    if (sum && pairs > (((uint64_t)1 << 61) - 1u) / sum) return fail(ctx, PG_EINVAL, "n_src * n_dst * sum of weights * 4 reaches 2^63");
+    *result = pg_reach_rules_result{E.layout_gen, 0, 0, c->n_slots, 0, 0};
+    if (c->empty) return PG_OK;
+    c->n_rule_slots = (uint32_t)std::count_if(E.slot_rule.begin(), E.slot_rule.end(), [](int32_t r) { return r >= 0; });
+    result->n_cells = pairs * sum, result->n_rule_slots = c->n_rule_slots;
+    c->svc = reach_services(&c->reach);
+    return PG_OK;
+}
+
+// n_evals and n_dead_rules of a finished call from its evaluation counts
+void rules_result(const Engine& E, const uint64_t* evals, pg_reach_rules_result* result) {
+    for (uint32_t s = 0; s < result->n_slots; s++) {
+        result->n_evals += evals[s];
+        if (E.slot_rule[s] >= 0 && !evals[s]) result->n_dead_rules++;
+    }
+}
+
+void host_rules_flush(uint32_t* win, const RulesWindow& w, uint32_t n, unsigned long long* out) {
+    for (uint32_t c = 0; c < w.cells; c++) {
+        if (win[c]) out[rules_index_of_cell(w, n, c)] += win[c];
+        win[c] = 0;
+    }
+}
+
+// every word of the services of one form, workgroup by workgroup and round by round as k_rules_pairs
+// runs them, the window cells flushed where the kernel flushes them. -> a cell wrapped
+template <bool UNI, bool WIDE, bool EVALS, bool CELLS>
+bool host_rules_pairs(const DevTableSet& T, const ReachPass& P, const RulesArgs& A) {
+    const uint32_t rw = (uint32_t)reach_row_words(P.n_dst);
+    const uint64_t n_words = (uint64_t)P.n_list * P.n_src * rw, step = (uint64_t)kRulesHostGrid * kRulesBlock;
+    const DevLoader img{T.node.img};
+    std::vector<uint32_t> win((size_t)A.evals.cells + A.cells.cells + 1u);
+    uint32_t *we = win.data(), *wc = win.data() + A.evals.cells;
+    bool wrapped = false;
+    auto flush = [&]() {
+        if (EVALS) host_rules_flush(we, A.evals, A.n_slots, A.out_evals);
+        if (CELLS) host_rules_flush(wc, A.cells, 4u * A.n_slots, A.out_cells);
+    };
+    for (uint32_t b = 0; b < kRulesHostGrid; b++) {
+        uint32_t since = 0;
+        for (uint64_t w0 = (uint64_t)b * kRulesBlock; w0 < n_words; w0 += step) {
+            if (since + kRulesBlock > A.flush_words) flush(), since = 0;
+            since += kRulesBlock;
+            for (uint64_t w = w0; w < std::min<uint64_t>(w0 + kRulesBlock, n_words); w++) {
+                const RulesWord x = rules_word_of(w, n_words, rw, P.n_src);
+                const uint32_t v = P.svc_list[x.k], j0 = x.jw * kReachWordPairs, wgt = A.weight[v];
+                const RulesSink<false> se{we, A.out_evals, A.evals, A.n_slots, wgt, &wrapped};
+                const RulesSink<false> sc{wc, A.out_cells, A.cells, 4u * A.n_slots, wgt, &wrapped};
+                if constexpr (UNI)
+                    rules_word_uni<WIDE, EVALS, CELLS>(T, T.node, img, P.rec_s[x.i], P.cls_s[x.i], P.rec_d, P.cls_d, j0, P.n_dst,
+                                                       P.svc[v], se, sc);
+                else
+                    rules_word_tab<EVALS, CELLS>(T, P.rec_s[x.i], P.rec_d, j0, P.n_dst, P.svc[v], se, sc);
+            }
+        }
+        flush();
+    }
+    return wrapped;
+}
+template <bool UNI, bool WIDE>
+bool host_rules_form(const DevTableSet& T, const ReachPass& P, const RulesArgs& A) {
+    if (A.out_evals && A.out_cells) return host_rules_pairs<UNI, WIDE, true, true>(T, P, A);
+    if (A.out_evals) return host_rules_pairs<UNI, WIDE, true, false>(T, P, A);
+    return host_rules_pairs<UNI, WIDE, false, true>(T, P, A);
+}
+}  // namespace
+
+extern "C" {
+
+int pg_reach_rules(pg_ctx* ctx, const pg_reach_rules_spec* spec, uint64_t* out_evals, uint64_t* out_cells,
+                   pg_reach_rules_result* result, void* stream) {
+    GUARD_BEGIN
+    RulesCall c;
+    if (int rc = rules_args(ctx, spec, out_evals, out_cells, result, &c)) return rc;
+    DEVICE_GUARD(ctx);
+    int rc = ctx->eng.sync();
+    if (rc) return rc;
+    Engine& E = ctx->eng;
+    const DevTableSet& T = *E.view();
+    const ReachSpecDev rd{spec->src_ip, spec->dst_ip, c.svc.data(), (uint32_t)spec->n_src, (uint32_t)spec->n_dst,
+                          (uint32_t)spec->n_svc};
+    const RulesSpecDev sd{rd, c.weight.data(), c.n_slots, c.n_slots - c.n_rule_slots, c.max_weight};
+    std::string err;
+    std::vector<uint64_t> evals;
+    if (dev_reach_rules(T, E.tune, sd, reinterpret_cast<unsigned long long*>(out_evals),
+                        reinterpret_cast<unsigned long long*>(out_cells), &evals, stream, &err) != 0 ||
+        dev_mark_use(E.cur, stream, false, &err) != 0)
+        return fail(ctx, PG_EIO, err);
+    if (out_evals && !c.empty) rules_result(E, evals.data(), result);
+    return PG_OK;
+    GUARD_END(ctx)
+}
+
+int pg_debug_reach_rules_host(pg_ctx* ctx, const pg_reach_rules_spec* spec, uint64_t* out_evals, uint64_t* out_cells,
+                              pg_reach_rules_result* result, int flags) {
+    GUARD_BEGIN
+    RulesCall c;
+    if (int rc = rules_args(ctx, spec, out_evals, out_cells, result, &c)) return rc;
+    if (out_evals) std::fill(out_evals, out_evals + c.n_slots, (uint64_t)0);
+    if (out_cells) std::fill(out_cells, out_cells + 4u * (size_t)c.n_slots, (uint64_t)0);
+    if (c.empty) return PG_OK;
+    Engine& E = ctx->eng;
+    const DevTableSet T = host_view(E.host);
+    const uint32_t nv = (uint32_t)spec->n_svc;
+    const bool form_a = (flags & 1) && reach_form_a(T.node, E.tune);
+    std::vector<uint32_t> la, lb;  // the services of each form that weigh anything
+    for (uint32_t v = 0; v < nv; v++)
+        if (c.weight[v]) (form_a && c.svc[v].x <= 2u ? la : lb).push_back(v);
+    const RulesPlan plan = rules_plan(c.n_slots, c.n_slots - c.n_rule_slots, out_evals != nullptr, out_cells != nullptr,
+                                      E.tune.rules_hist_cells, c.max_weight);
+    const RulesArgs A{c.weight.data(), reinterpret_cast<unsigned long long*>(out_evals),
+                      reinterpret_cast<unsigned long long*>(out_cells), plan.evals, plan.cells, c.n_slots, plan.flush_words};
+    HostHoist H;
+    bool wrapped = false;
+    if (!la.empty()) {
+        const ReachEnds ends = H.run(true, T, c.reach, c.svc, la);
+        const ReachPass P{ends, H.g.data(), la.data(), (uint32_t)la.size(), nullptr, nullptr};
+        wrapped |= T.node.wide ? host_rules_form<true, true>(T, P, A) : host_rules_form<true, false>(T, P, A);
+    }
+    if (!lb.empty()) {
+        const ReachEnds ends = H.run(false, T, c.reach, c.svc, lb);
+        const ReachPass P{ends, H.g.data(), lb.data(), (uint32_t)lb.size(), nullptr, nullptr};
+        wrapped |= host_rules_form<false, false>(T, P, A);
+    }
+    if (wrapped) return fail(ctx, PG_EFAULT, "a 32-bit window cell wrapped between two flushes");
+    if (out_evals) rules_result(E, out_evals, result);
+    return PG_OK;
+    GUARD_END(ctx)
+}
+
+int pg_debug_reach_rules_plan(pg_ctx* ctx, uint32_t n_slots, uint32_t n_tail, int evals, int cells, uint32_t max_weight,
+                              pg_reach_rules_plan* plan, uint32_t* resident) {
+    if (!ctx || !plan) return PG_EINVAL;
+    GUARD_BEGIN
+    if ((!evals && !cells) || n_tail > n_slots || max_weight > kRulesMaxWeight)
+        return fail(ctx, PG_EINVAL, "no histogram, n_tail above n_slots or max_weight above 65536");
+    const RulesPlan p = rules_plan(n_slots, n_tail, evals != 0, cells != 0, ctx->eng.tune.rules_hist_cells, max_weight);
+    *plan = pg_reach_rules_plan{p.block, p.evals.cells, p.evals.base, p.cells.cells, p.cells.base, p.flush_words, p.lds_bytes};
+    if (resident) {
+        DEVICE_GUARD(ctx);
+        *resident = (uint32_t)dev_rules_resident(ctx->eng.tune, p.lds_bytes);
     }
     return PG_OK;
     GUARD_END(ctx)

@@ -257,6 +257,8 @@ struct Tuning {
     uint32_t hist_window = 4096;   // LDS hit-counter cells when the slots exceed the LDS histogram
     uint32_t launch_max_tuples = 0;  // tuples per k_classify launch at most (0 = kMaxLaunchTuples)
     uint32_t classes_hash_bits = 64;  // pg_reach_classes: low bits kept of every signature (0 = all equal; tests)
+    uint32_t rules_hist_cells = 16384;  // pg_reach_rules: cap of a workgroup's LDS cells (0 = global atomics only)
+    uint32_t rules_wave_agg = 1;      // pg_reach_rules: equal indices of a wave added with one atomic (0 = one per lane)
 };
 // The launch a SINGLE classify makes of one table: the k_classify STAGE its blob is walked
 // at and the hit-counter LDS histogram (device.hip launch_classify dispatches on it;

@@ -71,6 +71,8 @@ const Knob kKnobs[] = {
     {"hist_window", &Tuning::hist_window, 1, 16382, false},
     {"launch_max_tuples", &Tuning::launch_max_tuples, 0, (1 << 30) - 64, false},
     {"classes_hash_bits", &Tuning::classes_hash_bits, 0, 64, false},
+    {"rules_hist_cells", &Tuning::rules_hist_cells, 0, 16384, false},
+    {"rules_wave_agg", &Tuning::rules_wave_agg, 0, 1, false},
 };
 bool Knob::allowed(int v) const {
     if (field == &Tuning::lc_max_stride) return v == 12 || v == 16 || v == 18;

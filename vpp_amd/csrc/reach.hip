@@ -22,10 +22,17 @@
 //                 are one or two addresses per wave. The per-interval values are indexed by the
 //                 loop counter alone and arrive by scalar loads (the arrays are __restrict__
 //                 kernel arguments of their own for that). Prologues: k_reach_ends, k_reach_svcs
+//  k_rules_pairs  rule coverage (pg_reach_rules; rules.hpp): k_reach_pairs's word index space and
+//                 lane order, but nothing stored per cell -- a workgroup of four waves counts every
+//                 evaluation and every final word, times the service's weight, into two windows of
+//                 u32 cells in LDS and flushes them to the u64 outputs with global atomics at the
+//                 end of its run and whenever the plan's wrap bound is reached. Indices past a
+//                 window go to the outputs at once, aggregated per distinct index over the wave.
+//                 Prologues: k_reach_ends, k_reach_svcs
 //
-// No kernel takes or touches a hit counter.
+// No kernel takes or touches a hit counter (k_rules_pairs counts into the caller's arrays).
 //
-// Both drivers are four steps: stage the inputs in one scratch block (lay_out), run each form's
+// The three drivers are four steps: stage the inputs in one scratch block (lay_out), run each form's
 // prologue (run_prologue), launch its pair kernel (with_words_vec, grid_resident), Scratch::finish.
 #include <hip/hip_runtime.h>
 
@@ -37,6 +44,7 @@
 #include "hiputil.hpp"
 #include "ports.hpp"
 #include "reach.hpp"
+#include "rules.hpp"
 
 namespace pg {
 
@@ -166,7 +174,61 @@ __global__ __launch_bounds__(kReachPairBlock) void k_ports_pairs(DevTableSet T, 
     }
 }
 
-// ---- what both drivers are made of -------------------------------------------------------------------
+// rule coverage (rules.hpp): a workgroup's window cells to the output array, the cells cleared.
+// Between two barriers: no lane counts while another reads and clears
+__device__ __forceinline__ void rules_flush(uint32_t* win, const RulesWindow& w, uint32_t n, unsigned long long* out) {
+    for (uint32_t c = threadIdx.x; c < w.cells; c += kRulesBlock) {
+        const uint32_t v = win[c];
+        if (v) {
+            atomicAdd(&out[rules_index_of_cell(w, n, c)], (unsigned long long)v);
+            win[c] = 0;
+        }
+    }
+}
+
+// Every workgroup makes the same rounds of kRulesBlock words (a lane past n_words idles), so the
+// barriers of a flush are uniform. `since` counts whole rounds: a flush comes before the round that
+// could take the words since the last one past A.flush_words (rules_plan: no cell can wrap before)
+template <bool UNI, bool WIDE, bool EVALS, bool CELLS, bool AGG>
+__global__ __launch_bounds__(kRulesBlock) void k_rules_pairs(DevTableSet T, ReachPass P, RulesArgs A, uint64_t n_words) {
+    extern __shared__ uint32_t rules_win[];  // [evals cells | cells cells]
+    uint32_t *we = rules_win, *wc = rules_win + A.evals.cells;
+    for (uint32_t c = threadIdx.x; c < A.evals.cells + A.cells.cells; c += kRulesBlock) rules_win[c] = 0;
+    __syncthreads();
+    const uint32_t rw = (uint32_t)reach_row_words(P.n_dst);
+    const uint64_t step = (uint64_t)gridDim.x * kRulesBlock;
+    uint32_t since = 0;
+    for (uint64_t w0 = (uint64_t)blockIdx.x * kRulesBlock; w0 < n_words; w0 += step) {
+        if (since + kRulesBlock > A.flush_words) {
+            __syncthreads();
+            if (EVALS) rules_flush(we, A.evals, A.n_slots, A.out_evals);
+            if (CELLS) rules_flush(wc, A.cells, 4u * A.n_slots, A.out_cells);
+            __syncthreads();
+            since = 0;
+        }
+        since += kRulesBlock;
+        const uint64_t w = w0 + threadIdx.x;
+        if (w >= n_words) continue;
+        const RulesWord x = rules_word_of(w, n_words, rw, P.n_src);
+        const uint32_t v = P.svc_list[x.k], j0 = x.jw * kReachWordPairs, wgt = A.weight[v];
+        const uint2 gq = *reinterpret_cast<const uint2*>(P.svc + v);
+        const W2 g{gq.x, gq.y};
+        const uint4 sq = *reinterpret_cast<const uint4*>(P.rec_s + x.i);
+        const W4 rs{sq.x, sq.y, sq.z, sq.w};
+        const RulesSink<AGG> se{we, A.out_evals, A.evals, A.n_slots, wgt, nullptr};
+        const RulesSink<AGG> sc{wc, A.out_cells, A.cells, 4u * A.n_slots, wgt, nullptr};
+        if constexpr (UNI)
+            rules_word_uni<WIDE, EVALS, CELLS>(T, T.node, DevLoader{T.node.img}, rs, P.cls_s[x.i], P.rec_d, P.cls_d, j0, P.n_dst,
+                                               g, se, sc);
+        else
+            rules_word_tab<EVALS, CELLS>(T, rs, P.rec_d, j0, P.n_dst, g, se, sc);
+    }
+    __syncthreads();
+    if (EVALS) rules_flush(we, A.evals, A.n_slots, A.out_evals);
+    if (CELLS) rules_flush(wc, A.cells, 4u * A.n_slots, A.out_cells);
+}
+
+// ---- what the drivers are made of --------------------------------------------------------------------
 // The scratch block of a call is a row of sections, each starting 16-B aligned. Those filled by the
 // host are `copied`: they go in as one copy of the block's first `copied` bytes (a section between
 // them that the kernels fill is copied over as zeros first).
@@ -303,6 +365,110 @@ int dev_reach_ports(const DevTableSet& T, const Tuning& tu, const PortsSpecDev& 
     else pairs(std::true_type{}, std::false_type{});
     HIPCHK(hipGetLastError());
     return blk.finish(st, "port sweep", err);
+}
+
+namespace {
+// f(k_rules_pairs<UNI, WIDE, EVALS, CELLS, AGG>) for the histograms asked for and the "rules_wave_agg" knob
+template <bool UNI, bool WIDE, class F>
+void with_rules_kernel(bool evals, bool cells, bool agg, const F& f) {
+    auto pick = [&](auto ev, auto ce) {
+        if (agg) f(k_rules_pairs<UNI, WIDE, decltype(ev)::value, decltype(ce)::value, true>);
+        else f(k_rules_pairs<UNI, WIDE, decltype(ev)::value, decltype(ce)::value, false>);
+    };
+    if (evals && cells) pick(std::true_type{}, std::true_type{});
+    else if (evals) pick(std::true_type{}, std::false_type{});
+    else pick(std::false_type{}, std::true_type{});
+}
+}  // namespace
+
+int dev_rules_resident(const Tuning& tu, uint32_t lds_bytes) {
+    auto k = k_rules_pairs<false, false, true, true, true>;
+    if (lds_bytes > 48u * 1024u)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    const int g = grid_resident(k, (int)kRulesBlock, lds_bytes, ~(uint64_t)0 >> 1, tu.blocks_per_cu);
+    (void)hipGetLastError();  // (a failed occupancy query is answered by grid_resident's fall-back)
+    return g;
+}
+
+int dev_reach_rules(const DevTableSet& T, const Tuning& tu, const RulesSpecDev& spec, unsigned long long* out_evals,
+                    unsigned long long* out_cells, std::vector<uint64_t>* evals_host, void* stream, std::string* err) {
+    const ReachSpecDev& rs = spec.reach;
+    const uint32_t ns = rs.n_src, nd = rs.n_dst, nv = rs.n_svc, ne = ns + nd, n_slots = spec.n_slots;
+    hipStream_t st = (hipStream_t)stream;
+    if (out_evals) HIPCHK(hipMemsetAsync(out_evals, 0, (size_t)n_slots * sizeof(uint64_t), st));
+    if (out_cells) HIPCHK(hipMemsetAsync(out_cells, 0, 4u * (size_t)n_slots * sizeof(uint64_t), st));
+    auto read_back = [&]() -> int {
+        if (!out_evals || !evals_host) return 0;
+        evals_host->assign(n_slots, 0);
+        HIPCHK(hipMemcpy(evals_host->data(), out_evals, (size_t)n_slots * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        return 0;
+    };
+    if (!ns || !nd || !nv) {
+        HIPCHK(hipStreamSynchronize(st));
+        return read_back();
+    }
+    const bool form_a = reach_form_a(T.node, tu);
+    // the services of each form that weigh anything: list = [form A ..., form B ...]
+    std::vector<uint32_t> list;
+    for (uint32_t v = 0; v < nv; v++)
+        if (spec.weight[v] && form_a && rs.services[v].x <= 2u) list.push_back(v);
+    const uint32_t na = (uint32_t)list.size();
+    for (uint32_t v = 0; v < nv; v++)
+        if (spec.weight[v] && !(form_a && rs.services[v].x <= 2u)) list.push_back(v);
+    const uint32_t nb = (uint32_t)list.size() - na;
+    if (!na && !nb) {
+        HIPCHK(hipStreamSynchronize(st));
+        return read_back();
+    }
+    enum { IP, LIST, WT, CLS, SVC, REC, END, G };  // rec: form A's records, end: form B's ends
+    const auto l = lay_out({{4u * (size_t)ne, true}, {4u * (size_t)nv, true}, {4u * (size_t)nv, true},
+                            {4u * (size_t)ne, false}, {16u * (size_t)nv, true}, {16u * (size_t)ne, false},
+                            {16u * (size_t)ne, false}, {8u * (size_t)nv, false}});
+    std::vector<unsigned char> h(l.copied, 0);
+    std::copy(rs.src_ip, rs.src_ip + ns, reinterpret_cast<uint32_t*>(h.data() + l.off[IP]));
+    std::copy(rs.dst_ip, rs.dst_ip + nd, reinterpret_cast<uint32_t*>(h.data() + l.off[IP]) + ns);
+    std::copy(list.begin(), list.end(), reinterpret_cast<uint32_t*>(h.data() + l.off[LIST]));
+    std::copy(spec.weight, spec.weight + nv, reinterpret_cast<uint32_t*>(h.data() + l.off[WT]));
+    std::copy(rs.services, rs.services + nv, reinterpret_cast<W4*>(h.data() + l.off[SVC]));
+    Scratch blk;
+    if (Scratch::make(&blk, l.total, err) != 0) return -1;
+    unsigned char* d = blk.at<unsigned char>(0);
+    HIPCHK(hipMemcpy(d, h.data(), h.size(), hipMemcpyHostToDevice));
+    const uint32_t *ip = blk.at<uint32_t>(l.off[IP]), *dl = blk.at<uint32_t>(l.off[LIST]);
+    uint32_t* cls = blk.at<uint32_t>(l.off[CLS]);
+    const W4* svc = blk.at<W4>(l.off[SVC]);
+    W4 *rec = blk.at<W4>(l.off[REC]), *end = blk.at<W4>(l.off[END]);
+    W2* g = blk.at<W2>(l.off[G]);
+    const RulesPlan plan = rules_plan(n_slots, spec.n_tail, out_evals != nullptr, out_cells != nullptr, tu.rules_hist_cells,
+                                      spec.max_weight);
+    const RulesArgs A{blk.at<uint32_t>(l.off[WT]), out_evals, out_cells, plan.evals, plan.cells, n_slots, plan.flush_words};
+    int rc = 0;
+    // one form: its n services lst, its end-point records r and (form A) classes c
+    auto pass = [&](auto uni, auto wide, const uint32_t* lst, uint32_t n, W4* r, uint32_t* c) {
+        run_prologue<decltype(uni)::value>(T, ip, ne, svc, lst, n, r, c, g, st);
+        const ReachPass P{{r, r + ns, c, c ? c + ns : nullptr, ns, nd}, g, lst, n, nullptr, nullptr};
+        const uint64_t n_words = (uint64_t)n * ns * reach_row_words(nd);
+        with_rules_kernel<decltype(uni)::value, decltype(wide)::value>(
+            out_evals != nullptr, out_cells != nullptr, tu.rules_wave_agg != 0, [&](auto k) {
+                if (plan.lds_bytes > 48u * 1024u &&
+                    hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        (int)plan.lds_bytes) != hipSuccess)
+                    rc = -1;
+                const int grid = grid_resident(k, (int)kRulesBlock, plan.lds_bytes, n_words, tu.blocks_per_cu);
+                (void)hipGetLastError();  // (a failed occupancy query is answered by grid_resident's fall-back)
+                if (rc == 0) hipLaunchKernelGGL(k, dim3(grid), dim3(kRulesBlock), plan.lds_bytes, st, T, P, A, n_words);
+            });
+    };
+    if (na && T.node.wide) pass(std::true_type{}, std::true_type{}, dl, na, rec, cls);
+    else if (na) pass(std::true_type{}, std::false_type{}, dl, na, rec, cls);
+    if (nb) pass(std::false_type{}, std::false_type{}, dl + na, nb, end, nullptr);
+    if (rc != 0) {
+        if (err) *err = "rule coverage: the LDS window was refused";
+        return -1;
+    }
+    HIPCHK(hipGetLastError());
+    if (blk.finish(st, "rule coverage", err) != 0) return -1;
+    return read_back();
 }
 
 }  // namespace pg

@@ -545,6 +545,45 @@ def reach_classes(engine, matrix, n_svc, n_src, n_dst, src=True, dst=True, reps=
     return sc, dc, sr, dr, q, classes_result(res)
 
 
+# ---- rule coverage (include/policygpu.h pg_reach_rules) ---------------------------------------
+def rules_spec(src_ips, dst_ips, services, weights, n_slots):
+    """pg_reach_rules_spec over host arrays (reach_spec's, and the weights as u32 or None) -> (spec,
+    the arrays it points into: keep them alive for the call)"""
+    rs, keep = reach_spec(src_ips, dst_ips, services)
+    w = None if weights is None else np.ascontiguousarray(weights, dtype=np.uint32)
+    if w is not None and len(w) != len(services):
+        raise ValueError("one weight per service expected")
+    spec = _capi.pg_reach_rules_spec(rs.src_ip, rs.n_src, rs.dst_ip, rs.n_dst, rs.services, rs.n_svc,
+                                     w.ctypes.data if w is not None and len(w) else None, int(n_slots))
+    return spec, (keep, w)
+
+
+def rules_result(res):
+    return {"n_slots": res.n_slots, "layout_gen": res.layout_gen, "n_cells": res.n_cells, "n_evals": res.n_evals,
+            "n_rule_slots": res.n_rule_slots, "n_dead_rules": res.n_dead_rules}
+
+
+def reach_rules(engine, src_ips, dst_ips, services, weights=None, evals=True, cells=True, stream=None):
+    """Per-rule coverage of the product src x dst x services on the GPU (pg_reach_rules), without the
+    product: -> (evals, cells, result). ``evals`` an int64 tensor [n_slots], the weighted evalACL
+    evaluations each counter slot decided (what pg_classify CONN would add to zeroed counters over the
+    product's tuples); ``cells`` an int64 tensor [n_slots, 4], the weighted cells by deciding slot and
+    ConnAction (the histogram of reach_matrix's words); whichever was not asked for is None. ``weights``
+    (0 .. 65536 per service, None = 1) repeat a slice. result: {n_slots, layout_gen, n_cells, n_evals,
+    n_rule_slots, n_dead_rules}. The call never touches the hit counters."""
+    if not (evals or cells):
+        raise ValueError("at least one of evals and cells")
+    n_slots = engine.num_counter_slots()
+    spec, keep = rules_spec(src_ips, dst_ips, services, weights, n_slots)
+    ev = torch.empty(n_slots, dtype=torch.int64, device="cuda") if evals else None
+    ce = torch.empty((n_slots, 4), dtype=torch.int64, device="cuda") if cells else None
+    res = _capi.pg_reach_rules_result()
+    engine._ck(lib.pg_reach_rules(engine.h, C.byref(spec), ev.data_ptr() if evals else None,
+                                  ce.data_ptr() if cells else None, C.byref(res), _stream_ptr(stream)))
+    del keep
+    return ev, ce, rules_result(res)
+
+
 def unpack(out_u32):
     w = out_u32.astype(np.uint32)
     return (w >> 30).astype(np.int64), (w & 0x3FFFFFFF).astype(np.int64)

@@ -758,6 +758,91 @@ class Engine:
         members = lambda cls, pods, n: [[pods[k] for k in np.flatnonzero(cls == c)] for c in range(n)]
         return members(sc, src_pods, n_sc), members(dc, dst_pods, n_dc), D.unpack_reach(q, n_svc, n_sc, n_dc)
 
+    def debug_reach_rules_host(self, src_ips, dst_ips, services, weights=None, evals=True, cells=True, node=True,
+                               n_slots=None):
+        """TESTS ONLY: pg_reach_rules's per-word code, sink, windows and flushes run on the host
+        (pg_debug_reach_rules_host). -> (evals u64 [n_slots], cells u64 [n_slots, 4], result dict), None
+        for a histogram that was not asked for; the outputs are pre-filled with ones in every bit."""
+        import numpy as np
+        from . import device as D
+        n = self.num_counter_slots() if n_slots is None else n_slots
+        spec, keep = D.rules_spec(src_ips, dst_ips, services, weights, n)
+        ev = np.full(n, 0xFFFFFFFFFFFFFFFF, np.uint64) if evals else None
+        ce = np.full((n, 4), 0xFFFFFFFFFFFFFFFF, np.uint64) if cells else None
+        res = _capi.pg_reach_rules_result()
+        p = lambda x: x.ctypes.data_as(C.c_void_p) if x is not None else None
+        self._ck(lib.pg_debug_reach_rules_host(self.h, C.byref(spec), p(ev), p(ce), C.byref(res), int(node)))
+        del keep
+        return ev, ce, D.rules_result(res)
+
+    def debug_reach_rules_plan(self, n_slots, n_tail=2, evals=True, cells=True, max_weight=65536, resident=False):
+        """TESTS ONLY: the launch plan of pg_reach_rules (pg_debug_reach_rules_plan) -> {block, evals_cells,
+        evals_base, cells_cells, cells_base, flush_words, lds_bytes}, and with ``resident`` (needs the
+        GPU) the workgroups the device holds at once"""
+        plan, res = _capi.pg_reach_rules_plan(), C.c_uint32()
+        self._ck(lib.pg_debug_reach_rules_plan(self.h, int(n_slots), int(n_tail), int(evals), int(cells), int(max_weight),
+                                               C.byref(plan), C.byref(res) if resident else None))
+        out = {k: getattr(plan, k) for k, _ in _capi.pg_reach_rules_plan._fields_}
+        if resident:
+            out["resident"] = res.value
+        return out
+
+    def _coverage(self, src, dst, services, weights, host, max_services=4096):
+        """(evals [n_slots], cells [n_slots, 4]) as Python-int numpy arrays of one product, by as many
+        pg_reach_rules calls as ``max_services`` asks for, summed (on the device unless ``host``)"""
+        import numpy as np
+        from . import device as D
+        n = self.num_counter_slots()
+        ev, ce = None, None
+        for k0 in range(0, max(len(services), 1), max_services):
+            part = services[k0:k0 + max_services]
+            w = None if weights is None else weights[k0:k0 + max_services]
+            if host:
+                e1, c1, _ = self.debug_reach_rules_host(src, dst, part, w)
+            else:
+                e1, c1, _ = D.reach_rules(self, src, dst, part, w)
+            ev, ce = (e1, c1) if ev is None else (ev + e1, ce + c1)
+        if not host:
+            ev, ce = ev.cpu().numpy(), ce.cpu().numpy()
+        return ev.astype(np.uint64).reshape(n), ce.astype(np.uint64).reshape(n, 4)
+
+    def _coverage_report(self, ev, ce):
+        n = len(ev)
+        row = lambda s, k: (k, int(ev[s]), [int(x) for x in ce[s]])
+        acls, dead = {}, []
+        for name in self.ACLNames():
+            tid = lib.pg_table_id(self.h, _b(name))
+            if tid < 0:   # (an ACL no table was compiled for)
+                continue
+            base, n_rules, dflt = self.table_info(tid)
+            acls[name] = [row(base + k, k) for k in range(n_rules)] + [row(dflt, -1)]
+            dead += [(name, k) for k in range(n_rules) if not ev[base + k]]
+        return {"acls": acls, "no_acl": row(n - 2, None)[1:], "unresolved": row(n - 1, None)[1:], "dead_rules": dead}
+
+    def rule_coverage(self, src_pods, dst_pods, services, weights=None, host=False):
+        """Which rules do any work over these pods and services, and which are dead or shadowed: by one
+        pg_reach_rules call, without the reach matrix. -> {"acls": {ACL name: [(rule index, evals,
+        cells[4])]}, the rules in order and last (-1, ...) for the ACL's default deny; "no_acl" and
+        "unresolved": (evals, cells[4]) of the evaluations of an interface without an ACL and of the pairs
+        that fail before any; "dead_rules": [(ACL name, rule index)] that decided no evaluation}. evals:
+        the evalACL evaluations the rule decided; cells[c]: the pairs whose final verdict it gave, by
+        ConnAction. ``weights`` (per service, 0 .. 65536) count a service several times. Pods and
+        services as in reachability. ``host``: TESTS ONLY, the host twin."""
+        src, dst = self._pod_ips(src_pods), self._pod_ips(dst_pods)
+        return self._coverage_report(*self._coverage(src, dst, list(services), weights, host))
+
+    def rule_coverage_ports(self, src_pods, dst_pods, protocol, src_port=40000, host=False, max_services=4096):
+        """rule_coverage over all 65,536 dst ports of TCP (0) or UDP (1): the services are the first
+        ports of the elementary intervals (port_intervals) and the weights the interval lengths, so a
+        pair costs K evaluations, not 65,536. More than ``max_services`` intervals (the call's 4096 at
+        most) take several calls, summed on the device."""
+        import numpy as np
+        src, dst = self._pod_ips(src_pods), self._pod_ips(dst_pods)
+        lo = self.port_intervals(protocol)
+        lens = np.diff(np.append(lo.astype(np.int64), 65536)).astype(np.uint32)
+        services = [(int(protocol), int(src_port), int(p)) for p in lo]
+        return self._coverage_report(*self._coverage(src, dst, services, lens, host, min(int(max_services), 4096)))
+
     def debug_walk_stats(self, table_id, src, dst, dport, proto):
         """MEASUREMENT: per tuple, the loads a SINGLE launch on table_id makes of the table's
         structure (pg_debug_walk_stats) -> (lds_reads u32[n], mem_reads u32[n], launch STAGE)"""
