@@ -840,6 +840,80 @@ int pg_debug_reach_classes_host(pg_ctx* ctx, const pg_reach_classes_spec* spec, 
 int pg_debug_reach_classes_plan(pg_ctx* ctx, uint32_t n_dst, uint32_t* tile_words, uint32_t* chunk_rows,
                                 uint32_t* check_rows);
 
+/* ---- reachability zones: mutually reachable end points and their graph, on the device -------
+ * "Which end points can all reach each other, and how do those zones sit relative to one another?" The
+ * input is a pg_reach_closure out_packed (n rows of pg_reach_row_words(n) words, 2 bits per cell),
+ * which stays on the device.
+ *   R(i, j): cell (i, j) holds PG_CONN_ALLOW; every other code counts as "no". Cell (i, i) is a cell
+ *   like any other.
+ *   Mutual reach M(i, j) = R(i, j) and R(j, i). label(i) = the least member of {i} u { j : M(i, j) }.
+ *   Over a full closure (max_hops == 0) R is transitive, so label(i) is the least member of i's
+ *   strongly connected component of the ALLOW graph -- a lateral-movement zone: it falls as a whole
+ *   when one member does. An end point that lies on no cycle is a zone of its own.
+ *   Zones: the distinct values of label[], ascending, get the ids 0, 1, ... (numbering by first
+ *   appearance, as in pg_reach_classes): zone[0] == 0, the representatives (the least members) ascend,
+ *   and the ids depend on nothing but the input.
+ *   Any input is defined -- a max_hops-bounded closure, a one-hop matrix, random words -- and the call
+ *   stays inside its arrays on it: where R is not transitive the labels are still the formula above,
+ *   and n_broken counts the end points i with label(label(i)) != label(i). It is 0 on every full
+ *   closure. Duplicate end points are equal rows and columns; they share a zone only if that pod
+ *   reaches itself.
+ *   out_zone        device, required, n words: the zone id of every end point
+ *   out_rep         device, optional, capacity n words: the first n_zones entries are each zone's least
+ *                   member; nothing past that is written
+ *   out_size        device, optional, capacity n: the first n_zones entries are the number of i with
+ *                   out_zone[i] == z. Integer counts: exact, and the same on every run
+ *   out_reaches     device, optional, capacity n each: for zone z with representative r the first
+ *   out_reached_by  n_zones entries are the number of j with R(r, j) -- the end points the zone
+ *                   reaches, its blast radius -- and the number of i with R(i, r), its exposure
+ *   out_dag         device, optional, needs out_rep; capacity n * pg_reach_row_words(n) words. The first
+ *                   n_zones * pg_reach_row_words(n_zones) words are the zone graph in the audits'
+ *                   layout: cell (a, b) = PG_CONN_ALLOW iff R(rep[a], rep[b]), else PG_CONN_DENY_SYN, the
+ *                   padding bits of a row's last word zero; nothing past that is written. The
+ *                   diagonal cell (z, z) is ALLOW exactly for a zone whose members lie on a cycle. A
+ *                   valid before / after of pg_reach_diff where two graphs have one size
+ *   result          host, required
+ * The padding bits of the input rows are masked, never trusted. Like pg_reach_closure the call reads
+ * no table and triggers no compile, and it never touches the hit counters or their snapshots; ctx only
+ * names the device and its launch knobs ("blocks_per_cu"). It enqueues on hip_stream -- the bits of R
+ * and of its transpose into scratch, the labels, the numbering, the zone graph, whose launch takes
+ * its geometry from device memory -- and synchronises that stream once, at the end, because the
+ * counts come back to the host. n == 0: PG_OK, *result zeroed, nothing else written (the matrix may
+ * then be null). PG_EINVAL (pg_last_error says which): a null spec, matrix, out_zone or result; out_dag
+ * without out_rep; n above 2^15. PG_ENOMEM: the scratch allocation (two n x n bit matrices and a few
+ * words per end point) failed. */
+typedef struct pg_reach_zones_spec {
+    const uint32_t* matrix;   /* device: a pg_reach_closure out_packed, n rows of pg_reach_row_words(n) words; 4-B aligned, nothing more assumed */
+    uint32_t n;               /* end points, 0 .. 2^15 */
+} pg_reach_zones_spec;
+typedef struct pg_reach_zones_result {   /* host */
+    uint32_t n_zones;
+    uint32_t n_cyclic;        /* zones with R(rep, rep): their members lie on a cycle */
+    uint32_t n_multi;         /* zones of more than one member */
+    uint32_t largest;         /* the largest out_size */
+    uint32_t n_broken;        /* end points with label(label(i)) != label(i): 0 where R is transitive */
+} pg_reach_zones_result;
+int pg_reach_zones(pg_ctx* ctx, const pg_reach_zones_spec* spec, uint32_t* out_zone, uint32_t* out_rep, uint32_t* out_size,
+                   uint32_t* out_reaches, uint32_t* out_reached_by, uint32_t* out_dag, pg_reach_zones_result* result,
+                   void* hip_stream);
+/* TESTS ONLY -- never on the audit path: pg_reach_zones's per-word code and plan (zones.hpp, the
+ * functions the kernels and the launch call) on the host, work item by work item; matrix and every
+ * output are host arrays. Does not touch the device. */
+int pg_debug_reach_zones_host(pg_ctx* ctx, const pg_reach_zones_spec* spec, uint32_t* out_zone, uint32_t* out_rep,
+                              uint32_t* out_size, uint32_t* out_reaches, uint32_t* out_reached_by, uint32_t* out_dag,
+                              pg_reach_zones_result* result);
+/* TESTS ONLY: how a pg_reach_zones over n end points is cut, from the one function the launch itself
+ * uses (zones.hpp zones_plan): the rows and columns of a transpose tile and the tiles there are, the
+ * rows of a label work item and the work items there are. Launches nothing. */
+typedef struct pg_reach_zones_plan {
+    uint32_t tile_rows, tile_cols;   /* cells of the matrix one transpose tile covers */
+    uint32_t row_tiles, col_tiles;   /* bits_grid = row_tiles * col_tiles */
+    uint32_t bits_grid;
+    uint32_t label_rows, label_grid; /* rows of a label work item; work items */
+    uint32_t dag_grid;               /* the most workgroups the zone graph can need: one per zone */
+} pg_reach_zones_plan;
+int pg_debug_reach_zones_plan(pg_ctx* ctx, uint32_t n, pg_reach_zones_plan* plan);
+
 /* ---- rule coverage: per-rule histograms of a reach product, on the device --------------------
  * "Which rules do any work over my inventory, which are dead or shadowed, and which rule denies the
  * most pairs?" The product is pg_reach_matrix's (the pg_reach_spec fields: the same end-point

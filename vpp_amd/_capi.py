@@ -139,6 +139,21 @@ class pg_reach_classes_result(C.Structure):
     _fields_ = [("n_src_classes", C.c_uint32), ("n_dst_classes", C.c_uint32), ("rounds", C.c_uint32)]
 
 
+class pg_reach_zones_spec(C.Structure):
+    _fields_ = [("matrix", C.c_void_p), ("n", C.c_uint32)]
+
+
+class pg_reach_zones_result(C.Structure):
+    _fields_ = [("n_zones", C.c_uint32), ("n_cyclic", C.c_uint32), ("n_multi", C.c_uint32), ("largest", C.c_uint32),
+                ("n_broken", C.c_uint32)]
+
+
+class pg_reach_zones_plan(C.Structure):
+    _fields_ = [("tile_rows", C.c_uint32), ("tile_cols", C.c_uint32), ("row_tiles", C.c_uint32),
+                ("col_tiles", C.c_uint32), ("bits_grid", C.c_uint32), ("label_rows", C.c_uint32),
+                ("label_grid", C.c_uint32), ("dag_grid", C.c_uint32)]
+
+
 class pg_reach_rules_spec(C.Structure):
     _fields_ = [("src_ip", C.c_void_p), ("n_src", C.c_size_t), ("dst_ip", C.c_void_p), ("n_dst", C.c_size_t),
                 ("services", C.POINTER(pg_service)), ("n_svc", C.c_size_t), ("svc_weight", C.c_void_p),
@@ -327,6 +342,11 @@ _SIGS = {
                                               C.POINTER(pg_reach_classes_result)]),
     "pg_debug_reach_classes_plan": (C.c_int, [_P, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                               C.POINTER(C.c_uint32)]),
+    "pg_reach_zones": (C.c_int, [_P, C.POINTER(pg_reach_zones_spec), _P, _P, _P, _P, _P, _P,
+                                 C.POINTER(pg_reach_zones_result), _P]),
+    "pg_debug_reach_zones_host": (C.c_int, [_P, C.POINTER(pg_reach_zones_spec), _P, _P, _P, _P, _P, _P,
+                                            C.POINTER(pg_reach_zones_result)]),
+    "pg_debug_reach_zones_plan": (C.c_int, [_P, C.c_uint32, C.POINTER(pg_reach_zones_plan)]),
     "pg_reach_rules": (C.c_int, [_P, C.POINTER(pg_reach_rules_spec), _P, _P, C.POINTER(pg_reach_rules_result), _P]),
     "pg_debug_reach_rules_host": (C.c_int, [_P, C.POINTER(pg_reach_rules_spec), _P, _P,
                                             C.POINTER(pg_reach_rules_result), C.c_int]),

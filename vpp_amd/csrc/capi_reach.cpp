@@ -1,6 +1,6 @@
 // extern "C" boundary of the reachability audits (include/policygpu.h): the matrix, the rule
-// coverage, the port sweep, the diff, the closure, the groups, the paths and the classes, each with
-// the host twin the tests compare its kernels to.
+// coverage, the port sweep, the diff, the closure, the groups, the paths, the classes and the zones,
+// each with the host twin the tests compare its kernels to.
 #include <algorithm>
 #include <numeric>
 
@@ -12,6 +12,7 @@
 #include "paths.hpp"
 #include "ports.hpp"
 #include "rules.hpp"
+#include "zones.hpp"
 
 using namespace pg;
 
@@ -1070,6 +1071,143 @@ int pg_debug_reach_classes_plan(pg_ctx* ctx, uint32_t n_dst, uint32_t* tile_word
     if (!ctx || !tile_words || !chunk_rows || !check_rows) return PG_EINVAL;
     const ClassesPlan p = classes_plan(n_dst);
     *tile_words = p.tile_words, *chunk_rows = p.chunk_rows, *check_rows = p.check_rows;
+    return PG_OK;
+}
+
+}  // extern "C"
+
+// ---- reachability zones (zones.hpp) --------------------------------------------------------------
+namespace {
+static_assert(sizeof(pg_reach_zones_result) == sizeof(ZonesResult), "pg_reach_zones_result is zones.hpp's ZonesResult");
+static_assert(sizeof(pg_reach_zones_plan) == sizeof(ZonesPlan), "pg_reach_zones_plan is zones.hpp's ZonesPlan");
+
+// argument checks shared by pg_reach_zones and its host twin: PG_OK with *empty set when there is no
+// end point (then *result is zeroed here)
+int zones_args(pg_ctx* ctx, const pg_reach_zones_spec* spec, const uint32_t* out_zone, const uint32_t* out_rep,
+               const uint32_t* out_dag, pg_reach_zones_result* result, bool* empty) {
+    if (!ctx) return PG_EINVAL;
+    if (!spec || !out_zone || !result) return fail(ctx, PG_EINVAL, "null spec, out_zone or result");
+    if (out_dag && !out_rep) return fail(ctx, PG_EINVAL, "out_dag needs out_rep");
+    if (spec->n > kClosureMaxN) return fail(ctx, PG_EINVAL, "more than 2^15 end points");
+    *empty = !spec->n;
+    if (!*empty && !spec->matrix) return fail(ctx, PG_EINVAL, "null matrix");
+    if (*empty) *result = pg_reach_zones_result{0, 0, 0, 0, 0};
+    return PG_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int pg_reach_zones(pg_ctx* ctx, const pg_reach_zones_spec* spec, uint32_t* out_zone, uint32_t* out_rep, uint32_t* out_size,
+                   uint32_t* out_reaches, uint32_t* out_reached_by, uint32_t* out_dag, pg_reach_zones_result* result,
+                   void* stream) {
+    GUARD_BEGIN
+    bool empty = false;
+    if (int rc = zones_args(ctx, spec, out_zone, out_rep, out_dag, result, &empty)) return rc;
+    if (empty) return PG_OK;
+    DEVICE_GUARD(ctx);
+    const ZonesOutDev od{out_zone, out_rep, out_size, out_reaches, out_reached_by, out_dag};
+    std::string err;
+    ZonesResult r{0, 0, 0, 0, 0};
+    const int rc = dev_reach_zones(ctx->eng.tune.blocks_per_cu, spec->matrix, spec->n, od, &r, stream, &err);
+    if (rc != 0) return fail(ctx, rc == -2 ? PG_ENOMEM : PG_EIO, err);
+    *result = pg_reach_zones_result{r.n_zones, r.n_cyclic, r.n_multi, r.largest, r.n_broken};
+    return PG_OK;
+    GUARD_END(ctx)
+}
+
+int pg_debug_reach_zones_host(pg_ctx* ctx, const pg_reach_zones_spec* spec, uint32_t* out_zone, uint32_t* out_rep,
+                              uint32_t* out_size, uint32_t* out_reaches, uint32_t* out_reached_by, uint32_t* out_dag,
+                              pg_reach_zones_result* result) {
+    GUARD_BEGIN
+    bool empty = false;
+    if (int rc = zones_args(ctx, spec, out_zone, out_rep, out_dag, result, &empty)) return rc;
+    if (empty) return PG_OK;
+    const uint32_t n = spec->n, stride = closure_stride(n), bw = closure_bit_words(n), rw = (uint32_t)reach_row_words(n);
+    const ZonesPlan plan = zones_plan(n);
+    const bool counts = out_reaches || out_reached_by;
+    std::vector<uint32_t> B((size_t)n * stride, 0xA5A5A5A5u), BT((size_t)n * stride, 0xA5A5A5A5u);  // (every word is written below)
+    // every tile in order, as k_zones_bits_t runs it: the tile's words into `sh`, then per pair of word
+    // columns the ballots of the two 64-row halves, lane by lane
+    std::vector<uint32_t> sh((size_t)kZonesTileRows * kZonesTilePitch);
+    for (uint32_t it = 0; it < plan.bits_grid; it++) {
+        const uint32_t tr = it / plan.col_tiles, tc = it % plan.col_tiles, r0 = tr * kZonesTileRows, w0 = tc * kZonesTileWords;
+        for (uint32_t r = 0; r < kZonesTileRows; r++)
+            for (uint32_t wl = 0; wl < kZonesTileWords; wl++) {
+                const uint32_t i = r0 + r, w = w0 + wl;
+                uint32_t x = 0;
+                if (i < n && w < stride) {
+                    x = zones_bit_word(spec->matrix + (size_t)i * rw, rw, n, w);
+                    B[(size_t)i * stride + w] = x;
+                }
+                sh[(size_t)r * kZonesTilePitch + wl] = x;
+            }
+        for (uint32_t q = 0; q < kZonesTileWords; q++)
+            for (uint32_t k = 0; k < 32; k++) {
+                uint64_t b[2] = {0, 0};
+                for (uint32_t half = 0; half < 2; half++)
+                    for (uint32_t lane = 0; lane < 64; lane++)
+                        b[half] |= (uint64_t)zones_ballot_bit(sh[(size_t)(64u * half + lane) * kZonesTilePitch + q], k) << lane;
+                const uint32_t c = 32u * (w0 + q) + k;
+                if (c >= n) continue;
+                uint32_t* bt = &BT[(size_t)c * stride + 4u * tr];
+                bt[0] = (uint32_t)b[0], bt[1] = (uint32_t)(b[0] >> 32), bt[2] = (uint32_t)b[1], bt[3] = (uint32_t)(b[1] >> 32);
+            }
+    }
+    // every row, as k_zones_label's waves run it: passes of 64 words, the lowest lane with a bit
+    std::vector<uint32_t> label(n), mark(n, 0u), cnt_b(n, 0u), cnt_bt(n, 0u);
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t *rb = &B[(size_t)i * stride], *rt = &BT[(size_t)i * stride];
+        const uint32_t last = i >> 5, end = counts ? bw : last + 1u;
+        uint32_t lab = i;
+        bool found = false;
+        for (uint32_t w0 = 0; w0 < end && !(found && !counts); w0 += 64u)
+            for (uint32_t lane = 0; lane < 64u; lane++) {
+                const uint32_t w = w0 + lane;
+                if (w >= end) break;
+                if (counts) cnt_b[i] += (uint32_t)__builtin_popcount(rb[w]), cnt_bt[i] += (uint32_t)__builtin_popcount(rt[w]);
+                if (!found && w <= last && (rb[w] & rt[w])) lab = zones_label(i, w, rb[w] & rt[w]), found = true;
+            }
+        label[i] = lab, mark[lab] = 1u;
+    }
+    // as k_zones_number: the scan of the marks, then the ids, the sizes and the result
+    std::vector<uint32_t> zid(n, 0u), rep, size;
+    uint32_t cyclic = 0, broken = 0, multi = 0, largest = 0;
+    for (uint32_t j = 0; j < n; j++) {
+        if (!mark[j]) continue;
+        const uint32_t at = (uint32_t)rep.size();
+        zid[j] = at, rep.push_back(j);
+        if (out_rep) out_rep[at] = j;
+        if (out_reaches) out_reaches[at] = cnt_b[j];
+        if (out_reached_by) out_reached_by[at] = cnt_bt[j];
+        cyclic += zones_bit(&B[(size_t)j * stride], j);
+    }
+    const uint32_t n_zones = (uint32_t)rep.size();
+    size.assign(n_zones, 0u);
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t l = label[i], z = zid[l];
+        out_zone[i] = z, size[z]++;
+        broken += label[l] != l;
+    }
+    for (uint32_t z = 0; z < n_zones; z++) {
+        if (out_size) out_size[z] = size[z];
+        multi += size[z] > 1u, largest = std::max(largest, size[z]);
+    }
+    // as k_zones_dag: a zone per workgroup, a lane per output word
+    const uint32_t rwz = (uint32_t)reach_row_words(n_zones);
+    for (uint32_t a = 0; out_dag && a < n_zones; a++)
+        for (uint32_t ow = 0; ow < rwz; ow++)
+            out_dag[(size_t)a * rwz + ow] = zones_dag_word(&B[(size_t)rep[a] * stride], out_rep + 16u * ow, std::min(16u, n_zones - 16u * ow));
+    *result = pg_reach_zones_result{n_zones, cyclic, multi, largest, broken};
+    return PG_OK;
+    GUARD_END(ctx)
+}
+
+int pg_debug_reach_zones_plan(pg_ctx* ctx, uint32_t n, pg_reach_zones_plan* plan) {
+    if (!ctx || !plan) return PG_EINVAL;
+    if (n > kClosureMaxN) return fail(ctx, PG_EINVAL, "more than 2^15 end points");
+    const ZonesPlan p = zones_plan(n);
+    *plan = pg_reach_zones_plan{p.tile_rows, p.tile_cols, p.row_tiles, p.col_tiles, p.bits_grid, p.label_rows, p.label_grid, p.dag_grid};
     return PG_OK;
 }
 

@@ -545,6 +545,44 @@ def reach_classes(engine, matrix, n_svc, n_src, n_dst, src=True, dst=True, reps=
     return sc, dc, sr, dr, q, classes_result(res)
 
 
+# ---- reachability zones (include/policygpu.h pg_reach_zones) ---------------------------------
+def zones_result(res):
+    return {"n_zones": res.n_zones, "n_cyclic": res.n_cyclic, "n_multi": res.n_multi, "largest": res.largest,
+            "n_broken": res.n_broken}
+
+
+def reach_zones(engine, closure, n, reps=False, sizes=False, counts=False, dag=False, stream=None):
+    """The end points of a reach_closure result that can all reach each other, and the graph of those
+    zones, on the GPU (pg_reach_zones). ``closure`` is an int32 device tensor [n, row_words(n)] in the
+    audits' layout (reach_closure's packed result; any matrix of that shape is defined). -> (zone, rep,
+    size, reaches, reached_by, dag, result): the zone of every end point as an int32 tensor [n], numbered
+    by first appearance; with ``reps`` each zone's least member and with ``sizes`` its members, int32
+    tensors [n_zones]; with ``counts`` the end points each zone reaches and is reached by, two int32
+    tensors [n_zones]; with ``dag`` (it takes the representatives: they are returned too) the zone graph
+    as an int32 tensor [n_zones, row_words(n_zones)] in the audits' layout (unpack_closure, reach_diff);
+    and {n_zones, n_cyclic, n_multi, largest, n_broken}. Whatever was not asked for is None. The call
+    never touches the hit counters."""
+    rw = reach_row_words(n)
+    if closure.dtype != torch.int32 or not closure.is_contiguous() or closure.numel() != n * rw:
+        raise ValueError("a contiguous int32 tensor [n, row_words(n)] expected")
+    reps = reps or dag
+    new = lambda k: torch.empty(k, dtype=torch.int32, device="cuda")
+    zone = new(n)
+    rep, size = new(n) if reps else None, new(n) if sizes else None
+    out, by = (new(n), new(n)) if counts else (None, None)
+    graph = new(n * rw) if dag else None
+    res = _capi.pg_reach_zones_result()
+    if n:  # (an empty tensor has no address to hand over; the call would write nothing)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        engine._ck(lib.pg_reach_zones(engine.h, C.byref(_capi.pg_reach_zones_spec(closure.data_ptr(), int(n))), ptr(zone),
+                                      ptr(rep), ptr(size), ptr(out), ptr(by), ptr(graph), C.byref(res), _stream_ptr(stream)))
+    nz = res.n_zones
+    cut = lambda t: None if t is None else t[:nz]
+    if graph is not None:
+        graph = graph[:nz * reach_row_words(nz)].reshape(nz, reach_row_words(nz))
+    return zone, cut(rep), cut(size), cut(out), cut(by), graph, zones_result(res)
+
+
 # ---- rule coverage (include/policygpu.h pg_reach_rules) ---------------------------------------
 def rules_spec(src_ips, dst_ips, services, weights, n_slots):
     """pg_reach_rules_spec over host arrays (reach_spec's, and the weights as u32 or None) -> (spec,

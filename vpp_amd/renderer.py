@@ -758,6 +758,102 @@ class Engine:
         members = lambda cls, pods, n: [[pods[k] for k in np.flatnonzero(cls == c)] for c in range(n)]
         return members(sc, src_pods, n_sc), members(dc, dst_pods, n_dc), D.unpack_reach(q, n_svc, n_sc, n_dc)
 
+    def debug_reach_zones_host(self, closure, n, reps=True, sizes=True, counts=True, dag=True):
+        """TESTS ONLY: pg_reach_zones's per-word code and plan run on the host (pg_debug_reach_zones_host)
+        over a numpy array of packed words [n, row_words(n)]. -> (zone u32 [n], rep, size, reaches,
+        reached_by u32 [n_zones], dag words u32 [n_zones, row_words(n_zones)], {n_zones, n_cyclic, n_multi,
+        largest, n_broken}), None for what was not asked for (``dag`` takes the representatives)."""
+        import numpy as np
+        from . import device as D
+        m = np.ascontiguousarray(closure, dtype=np.uint32)
+        reps = reps or dag
+        new = lambda k: np.full(k, 0xFFFFFFFF, np.uint32)
+        zone = new(n)
+        rep, size = new(n) if reps else None, new(n) if sizes else None
+        out, by = (new(n), new(n)) if counts else (None, None)
+        graph = new(m.size) if dag else None
+        res = _capi.pg_reach_zones_result()
+        if n:
+            p = lambda x: x.ctypes.data_as(C.c_void_p) if x is not None else None
+            spec = _capi.pg_reach_zones_spec(m.ctypes.data, int(n))
+            self._ck(lib.pg_debug_reach_zones_host(self.h, C.byref(spec), p(zone), p(rep), p(size), p(out), p(by), p(graph),
+                                                   C.byref(res)))
+        nz = res.n_zones
+        rwz = lib.pg_reach_row_words(nz)
+        cut = lambda x: None if x is None else x[:nz]
+        return (zone, cut(rep), cut(size), cut(out), cut(by), None if graph is None else graph[:nz * rwz].reshape(nz, rwz),
+                D.zones_result(res))
+
+    def debug_reach_zones_plan(self, n):
+        """TESTS ONLY: how pg_reach_zones over n end points is cut (pg_debug_reach_zones_plan) ->
+        {tile_rows, tile_cols, row_tiles, col_tiles, bits_grid, label_rows, label_grid, dag_grid}"""
+        p = _capi.pg_reach_zones_plan()
+        self._ck(lib.pg_debug_reach_zones_plan(self.h, int(n), C.byref(p)))
+        return {name: getattr(p, name) for name, _ in p._fields_}
+
+    def _zones(self, ips, services, host, **kw):
+        """one _closure (max_hops 0) and one pg_reach_zones over it -> (closure words, reach_zones's
+        tuple), device tensors or with ``host`` numpy arrays"""
+        from . import device as D
+        packed, _, _ = self._closure(ips, services, 0, host, False)
+        if host:
+            return packed, self.debug_reach_zones_host(packed, len(ips), **kw)
+        return packed, D.reach_zones(self, packed, len(ips), **kw)
+
+    def reachability_zones(self, pods, services, host=False):
+        """Lateral-movement zones: the pods that can all reach each other in any number of hops over
+        ``services`` (the strongly connected components of the ALLOW graph), and how the zones sit to one
+        another, by one pg_reach_matrix over pods x pods, one pg_reach_closure and one pg_reach_zones. ->
+        (zones, reaches, reached_by, graph): the zones as lists of pods, in the order of their first member
+        and every zone's members in list order (a pod that lies on no cycle is a zone of its own); per
+        zone the number of listed pods it reaches (its blast radius) and that reach it (its exposure),
+        uint32 arrays [n_zones]; and the bool array [n_zones, n_zones], graph[a, b] = zone a reaches zone b
+        (graph[z, z]: the zone's members lie on a cycle). Pods and services as in reachability. ``host``:
+        TESTS ONLY, the host twins."""
+        import numpy as np
+        from . import device as D
+        ips = self._pod_ips(pods)
+        n = len(ips)
+        if n == 0 or not services:
+            # (no edge: every pod is a zone that reaches nothing)
+            return [[p] for p in pods], np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros((n, n), bool)
+        _, (zone, _, _, out, by, graph, res) = self._zones(ips, services, host, reps=False, sizes=False, counts=True, dag=True)
+        if not host:
+            zone, out, by = (t.cpu().numpy().view(np.uint32) for t in (zone, out, by))
+        nz = res["n_zones"]
+        members = [[pods[k] for k in np.flatnonzero(zone == z)] for z in range(nz)]
+        return members, out, by, D.unpack_closure(graph, nz)
+
+    def reachability_zones_diff(self, baseline, pods, services, host=False):
+        """Which zones a policy change connected or cut: the zones are those under ``baseline`` (another
+        Engine on the same device); the closure under the baseline and the closure under this engine are
+        each summed into (zone, zone) pairs by pg_reach_groups, and one pg_reach_diff over the two
+        summaries lists the pairs whose status moved. -> [(src zone, dst zone, status before, after), ...]
+        in (src zone, dst zone) order, the zones as lists of pods as reachability_zones gives them for the
+        baseline; the status is GROUPS_NONE / SOME / ALL of the zone pair's (src pod, dst pod) cells
+        reachable (before, a pair is NONE or ALL; after, SOME says that only a part of the two zones got
+        connected or stayed so). At most 4096 zones. ``host``: TESTS ONLY, the host twins."""
+        import numpy as np
+        from . import device as D
+        ips = self._pod_ips(pods)
+        n = len(ips)
+        if n == 0 or not services:
+            return []
+        b, (zone, _, _, _, _, _, res) = baseline._zones(ips, services, host, reps=False, sizes=False, counts=False, dag=False)
+        a, _, _ = self._closure(ips, services, 0, host, False)
+        nz = res["n_zones"]
+        if host:
+            sb, sa = (self.debug_reach_groups_host(m.reshape(1, n, -1), n, n, zone, zone, nz, nz)[1] for m in (b, a))
+            k, changes, _, _ = self.debug_reach_diff_host(sb, sa, nz, row_changes=False)
+            changes = changes[:k]
+        else:
+            zone = zone.cpu().numpy().view(np.uint32)
+            sb, sa = (D.reach_groups(self, m.reshape(1, n, -1), n, n, zone, zone, nz, nz, packed=True)[1] for m in (b, a))
+            _, changes, _, _ = D.reach_diff(self, sb, sa, nz)
+        members = [[pods[k] for k in np.flatnonzero(zone == z)] for z in range(nz)]
+        row, col, cb, ca = D.unpack_changes(changes)
+        return [(members[int(r)], members[int(j)], int(x), int(y)) for r, j, x, y in zip(row, col, cb, ca)]
+
     def debug_reach_rules_host(self, src_ips, dst_ips, services, weights=None, evals=True, cells=True, node=True,
                                n_slots=None):
         """TESTS ONLY: pg_reach_rules's per-word code, sink, windows and flushes run on the host
