@@ -210,7 +210,12 @@ int pg_set_host_interconnect_if_name(pg_ctx* ctx, const char* if_name);
 int pg_set_main_interface_name(pg_ctx* ctx, const char* if_name);
 int pg_set_other_vpp_interfaces(pg_ctx* ctx, const char* const* if_names, size_t n);
 int pg_set_vxlan_bvi_if_name(pg_ctx* ctx, const char* if_name);
-/* MockACLEngine.RegisterPod */
+/* MockACLEngine.RegisterPod. pg_classify's PERPOD / CONN modes and the reachability audits resolve
+ * an IPv4 address to the pod registered with it. Of several pods registered with one address the
+ * last in PodID order (namespace, then name; not the order of the calls) answers for it, whatever
+ * its kind: a pod of another node takes a local pod's address over and the other way round, a
+ * local pod without an interface makes it unresolvable. (The reference keeps pods by ID and has no
+ * such rule; pg_connections, which takes pod IDs, is not affected.) */
 int pg_register_pod(pg_ctx* ctx, const char* pod_namespace, const char* pod_name, const char* ip, int another_node);
 
 /* ---- renderer (PolicyRendererAPI) -------------------------------------------------- */
@@ -271,6 +276,17 @@ int pg_debug_classify_host(pg_ctx* ctx, int mode, int table_id, const pg_tuple_s
                            uint32_t* out, uint64_t* counters, int flags);
 /* TESTS ONLY, the same for the reachability matrix: pg_debug_reach_matrix_host, declared with
  * pg_reach_matrix below. */
+/* TESTS ONLY -- never on the classify path: where the end-point table (the open-addressing hash
+ * over the registered pods' IPv4 addresses that the per-table path, the node kernels' ANY-protocol
+ * pass and form B of the reachability audits resolve an address with) finds each of n addresses,
+ * read off the compiled host image by a plain loop: out_slot[i] = the cell the probe of ips[i]
+ * starts at, out_steps[i] = the 16-byte cells it reads until it hits the address or an empty cell
+ * (1 = the first cell decides), *out_cap = the table's cells (a power of two; a probe wraps from
+ * cell cap - 1 to cell 0). Any output may be null. Tests use it to show that their addresses reach
+ * a collision chain, a wrap or a long miss -- never for an expected verdict. Does not touch the
+ * device. */
+int pg_debug_endpoint_probe(pg_ctx* ctx, const uint32_t* ips, uint64_t n, uint32_t* out_steps, uint32_t* out_slot,
+                            uint32_t* out_cap);
 /* TESTS ONLY -- never on the classify path: install n host counters (e.g. from
  * pg_debug_classify_host) as the LOCAL or CLUSTER snapshot in the currently compiled slot layout,
  * so the snapshot readers below can be tested without a GPU. n must equal the slot count. */

@@ -9,7 +9,9 @@ pair of end points also picks the reference's call: pod <-> pod is ConnectionPod
 registered on another node paired with a non-pod address is those calls' "invalid scenario"
 and returns ConnActionFailure before any evaluation (:343-347, :388-392). Non-pod <-> non-pod
 has no reference call; the engine's convention is the same FAILURE. Both count
-once at the "unresolved" slot, like the other preamble failures. The engine is only read
+once at the "unresolved" slot, like the other preamble failures. Of pods registered with one
+address the last in PodID order answers for it (winners(): the engine's rule, the reference has
+none). The engine is only read
 through its public introspection calls (ACL names, ACL dumps, interface bindings, slot
 layout) and the pod registrations the test made (RegisterPod), never through its classifier.
 """
@@ -21,13 +23,49 @@ from . import gonet
 LOCAL, REMOTE, INET = 0, 1, 2  # end-point kinds
 
 
+def pod_order(pod):
+    """the engine's PodID order of a "namespace/name": by namespace, then by name"""
+    ns, _, name = pod.partition("/")
+    return ns, name
+
+
+def winners(pods):
+    """pods: (pod "namespace/name", IPv4 u32, TAP name or None, on another node) of every
+    registration -> {address: (TAP or None, on another node)}. The reference keeps pods by ID and
+    never asks which pod an address belongs to; the engine does (its tuples carry addresses), and
+    its rule for pods registered with one address is: the last of them in PodID order answers for
+    the address, whatever its kind (include/policygpu.h pg_register_pod)."""
+    out = {}
+    for pod, ip, tap, another in sorted(pods, key=lambda p: pod_order(p[0])):
+        out[int(ip)] = (tap, bool(another))
+    return out
+
+
 class World:
-    def __init__(self, engine, local_ifs, node_if, no_if_ips=(), remote_ips=None):
+    def __init__(self, engine, local_ifs, node_if, no_if_ips=(), remote_ips=None, pods=None):
         """local_ifs: {IPv4 u32: TAP name} of the pods on this node; node_if: name or None;
         no_if_ips: IPv4s of pods on this node whose interface is unknown (unresolvable:
         "Missing interface for ... pod", aclengine_mock.go:302-306 -> FAILURE); remote_ips:
         IPv4s of pods on another node (default: the engine's RegisterPod calls with
-        anotherNode set)."""
+        anotherNode set). pods: every registration as winners() takes it, instead of the three
+        (for worlds in which pods share an address: winners() decides whose it is). Without
+        `pods` an address given both as a pod of this node and, by the engine's RegisterPod
+        calls, as one of another node goes to the last of those pods in PodID order as well."""
+        if pods is not None:
+            won = winners(pods)
+            local_ifs = {ip: tap for ip, (tap, another) in won.items() if not another and tap is not None}
+            no_if_ips = [ip for ip, (tap, another) in won.items() if not another and tap is None]
+            remote_ips = [ip for ip, (_, another) in won.items() if another and node_if]
+        if remote_ips is None:
+            last = {}
+            for pod, (ip, another) in sorted(getattr(engine, "registered_pods", {}).items(), key=lambda kv: pod_order(kv[0])):
+                v4 = gonet.to4(gonet.parse_ip(ip) or b"")
+                if v4 is not None and (node_if or not another):   # (no node-output interface: not an end point)
+                    last[gonet.ipv4_u32(v4)] = another
+            remote_ips = [ip for ip, another in last.items() if another]
+            # (local addresses a pod of another node, later in PodID order, took over)
+            local_ifs = {ip: tap for ip, tap in local_ifs.items() if ip not in remote_ips}
+            no_if_ips = [ip for ip in no_if_ips if ip not in remote_ips]
         self.names = engine.ACLNames()
         self.acls = [fast.OraACL(engine.GetACLByName(n)["rules"]) for n in self.names]
         tix = {n: i for i, n in enumerate(self.names)}
@@ -40,13 +78,7 @@ class World:
         self.local_ips = np.array(ips, np.uint32)
         self.local_if = np.array([self.ifx[local_ifs[ip]] if ip in local_ifs else -1 for ip in ips], np.int32)
         self.node = self.ifx[node_if] if node_if else -1
-        if remote_ips is None:
-            remote_ips = []
-            for ip, another in getattr(engine, "registered_pods", {}).values():
-                v4 = gonet.to4(gonet.parse_ip(ip) or b"")
-                if another and v4 is not None:
-                    remote_ips.append(gonet.ipv4_u32(v4))
-        self.remote_ips = np.array(sorted(set(int(x) for x in remote_ips) - set(ips)), np.uint32)
+        self.remote_ips =np.array(sorted(set(int(x) for x in remote_ips) - set(ips)), np.uint32)
         # slot layout of the engine (pg_table_info / pg_num_counter_slots)
         self.tids = [engine.table_id(n) for n in self.names]  # engine table id of each oracle table
         info = [engine.table_info(t) for t in self.tids]

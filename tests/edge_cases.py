@@ -758,6 +758,15 @@ def reach_edges(topology):
     return ReachEdges(topology)
 
 
+@functools.lru_cache(maxsize=None)
+def reach_edge_hists(topology):
+    """the oracle's rule-coverage histograms of a topology's edge product, summed over its services at
+    weight 1: (evals [n_slots], cells [n_slots, 4]) (rules_cases.slice_hists)"""
+    import rules_cases as kr
+    r = reach_edges(topology)
+    return kr.weighted(*kr.slice_hists(r.t.world, r.src, r.dst, r.svc))
+
+
 # topology -> (ConnActions present, end-point pair cells that differ, port pair cells that differ)
 REACH_MEASURED = {
     "big-dst": ([0, 1, 2, 3], 29872, 7020),

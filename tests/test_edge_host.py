@@ -4,9 +4,9 @@
 The preconditions come from the oracle alone: decisive pairs per field kind at or above the floor,
 every edge cell of every probed rule hit, the share of single-rule mutations the batch sees, each
 equal to what edge_cases.MEASURED records; the structure and stage codes written down for the edge
-tables; pg_debug_classify_host (SINGLE, PERPOD, CONN), pg_debug_reach_matrix_host and
-pg_debug_reach_ports_host on the edge batches against the oracle, bit for bit; and the C oracle
-itself on the probes against the pure-Python evalACL.
+tables; pg_debug_classify_host (SINGLE, PERPOD, CONN), pg_debug_reach_matrix_host,
+pg_debug_reach_ports_host and pg_debug_reach_rules_host on the edge batches against the oracle, bit
+for bit; and the C oracle itself on the probes against the pure-Python evalACL.
 """
 import functools
 
@@ -18,6 +18,7 @@ import edge_cases as ec
 import node_matrix as nm
 import ports_cases as pc
 import reach_cases as rc
+import rules_cases as kr
 import single_matrix as sm
 
 TOPOLOGIES = sorted({sp.topology for sp in nm.SETS.values()})
@@ -279,3 +280,16 @@ def test_reach_ports_host_equals_oracle(name, protocol):
     assert (words == first).all(), pc.mismatch_report(words, first)
     assert (codes == pc.pack(first >> 30)).all()
     assert (n_open == (((first >> 30) == pc.ALLOW) * pc.lengths(lo)).sum(axis=2)).all()
+
+
+@pytest.mark.parametrize("name", REACH_SETS)
+def test_reach_rules_host_equals_oracle(name):
+    """rule coverage of the edge product: evals and cells, together and each alone"""
+    s = nm.node_set(name)
+    r = ec.reach_edges(s.spec.topology)
+    wev, wce = ec.reach_edge_hists(s.spec.topology)
+    kr.check_preconditions(name, wev, wce)
+    for evals, cells in ((True, True), (True, False), (False, True)):
+        got = kr.run_host(s.e, r.src, r.dst, r.svc, evals=evals, cells=cells)
+        kr.same(got, wev, wce, (name, evals, cells))
+        assert got[2] == kr.want_result(s.e, r.src, r.dst, np.ones(len(r.svc)), wev, evals=evals)

@@ -12,8 +12,9 @@ by tests/test_edge_host.py (decisive pairs, 100 % edge-cell coverage, sensitivit
            ladder-src
   PERPOD / CONN   every set of node_matrix.SETS x mode x counters at the default launch, stage0 and
            the per-table path
-  reach    pg_reach_matrix (packed and full words) and pg_reach_ports (TCP, UDP) over sides and
-           services of edge addresses and ports, for reach_cases' form A and form B sets
+  reach    pg_reach_matrix (packed and full words), pg_reach_ports (TCP, UDP) and pg_reach_rules (evals
+           and cells) over sides and services of edge addresses and ports, for reach_cases' form A and
+           form B sets
 """
 import numpy as np
 import pytest
@@ -23,6 +24,7 @@ import edge_cases as ec
 import node_matrix as nm
 import ports_cases as pc
 import reach_cases as rc
+import rules_cases as kr
 import single_matrix as sm
 import test_gpu_fd_pipeline as fp
 
@@ -154,3 +156,17 @@ def test_reach_ports_edges(name, protocol):
     assert (words == first).all(), pc.mismatch_report(words, first)
     assert (codes == pc.pack(first >> 30)).all(), "codes differ from the words' top two bits"
     assert (n_open == (((first >> 30) == pc.ALLOW) * pc.lengths(lo)).sum(axis=2)).all()
+
+
+@pytest.mark.parametrize("name", REACH_SETS)
+def test_reach_rules_edges(name):
+    """rule coverage of the edge product against the oracle and, byte for byte, the host twin"""
+    import test_gpu_rules as gr
+    s = nm.node_set(name)
+    r = ec.reach_edges(s.spec.topology)
+    wev, wce = ec.reach_edge_hists(s.spec.topology)
+    for evals, cells in ((True, True), (True, False), (False, True)):
+        got = gr.run_dev(s.e, r.src, r.dst, r.svc, evals=evals, cells=cells)
+        kr.same(got, wev, wce, (name, evals, cells))
+        gr.identical(got, kr.run_host(s.e, r.src, r.dst, r.svc, evals=evals, cells=cells), (name, evals, cells))
+        assert got[2] == kr.want_result(s.e, r.src, r.dst, np.ones(len(r.svc)), wev, evals=evals)

@@ -725,6 +725,30 @@ int pg_debug_classify_host(pg_ctx* ctx, int mode, int table_id, const pg_tuple_s
     GUARD_END(ctx)
 }
 
+int pg_debug_endpoint_probe(pg_ctx* ctx, const uint32_t* ips, uint64_t n, uint32_t* out_steps, uint32_t* out_slot,
+                            uint32_t* out_cap) {
+    if (!ctx || (!ips && n)) return PG_EINVAL;
+    GUARD_BEGIN
+    Engine& E = ctx->eng;
+    if (!E.compiled) E.compile();
+    const HostTableSet& h = E.host;
+    const uint32_t cap = h.iphash_mask + 1u;
+    if (h.iphash.size() != 4 * (size_t)cap) return fail(ctx, PG_EINVAL, "no end-point table");
+    if (out_cap) *out_cap = cap;
+    for (uint64_t i = 0; i < n; i++) {
+        uint32_t s = hash_ip(ips[i]) & h.iphash_mask, steps = 1;
+        if (out_slot) out_slot[i] = s;
+        // (a cell is 16 bytes: {address, interface, inbound table, outbound table}; empty: interface ~0)
+        while (h.iphash[4 * (size_t)s + 1] != 0xFFFFFFFFu && h.iphash[4 * (size_t)s] != ips[i] && steps <= cap) {
+            s = (s + 1) & h.iphash_mask;
+            steps++;
+        }
+        if (out_steps) out_steps[i] = steps;
+    }
+    return PG_OK;
+    GUARD_END(ctx)
+}
+
 int pg_debug_set_snapshot(pg_ctx* ctx, int which, const uint64_t* counters, size_t n) {
     if (!ctx || (!counters && n) || (which != PG_SNAP_LOCAL && which != PG_SNAP_CLUSTER)) return PG_EINVAL;
     GUARD_BEGIN

@@ -397,7 +397,8 @@ bool build_fd_blob(const TableAnalysis& an, uint32_t dflt, const Tuning& tu, std
                    uint32_t max_words, uint32_t lds_words);
 // fastpath.cpp: the node classifier over the tables with an analysis (null = not covered).
 // pods: {IPv4, interface (with its kEnd* kind), inbound table, outbound table} of registered
-// pods; node_end: the same for every other address. false = over budget (h.node_img left empty).
+// pods; node_end: the same for every other address. false = over a budget: no node, that is
+// h.node_img, h.node_cross and h.node_aux empty and h.node zeroed, whichever budget it was.
 struct NodePod {
     uint32_t ip;
     int32_t ifc, tin, tout;

@@ -1018,13 +1018,20 @@ void build_common_rows(HostTableSet& h, const std::vector<uint32_t>& cov, const 
     N.img_words = (uint32_t)img.size();
 }
 
-bool build_node(HostTableSet& h, const std::vector<TableAnalysis*>& an, const std::vector<NodePod>& pods,
-                const NodePod& node_end, const Tuning& tu) {
+static void clear_node(HostTableSet& h) {
     h.node_img.clear();
     h.node_aux.clear();
     h.node_cross.clear();
     h.node = DevNode{};
     h.node_rec_words = 0;
+    h.node_list_tab_words = 0;
+}
+
+// the builder proper: it writes straight into h and leaves at the first budget it exceeds, with
+// whatever it had built by then still in h -- only build_node may call it
+static bool build_node_image(HostTableSet& h, const std::vector<TableAnalysis*>& an, const std::vector<NodePod>& pods,
+                             const NodePod& node_end, const Tuning& tu) {
+    clear_node(h);
     const uint32_t T = (uint32_t)h.tabs.size();
     if (!tu.node_build || T == 0 || T >= 0xFFFFu) return false;
     std::vector<uint32_t> cov;
@@ -1270,7 +1277,7 @@ bool build_node(HostTableSet& h, const std::vector<TableAnalysis*>& an, const st
     if (aligned && !uni) {  // (the aligned tries are the uniform layout's): the other layout
         Tuning t2 = tu;
         t2.node_uniform = 0;
-        return build_node(h, an, pods, node_end, t2);
+        return build_node_image(h, an, pods, node_end, t2);
     }
     if (uni) entries = (uint64_t)T * G * GK;
     // L4-key trie: aligned, the root stride (18 - root a multiple of 4, at most
@@ -1452,7 +1459,7 @@ bool build_node(HostTableSet& h, const std::vector<TableAnalysis*>& an, const st
             Tuning t2 = tu;
             t2.node_list_table = 0;
             t2.node_uniform = 0;
-            return build_node(h, an, pods, node_end, t2);
+            return build_node_image(h, an, pods, node_end, t2);
         }
         N.lv0 = (uint32_t)X.size();
         h.node_list_tab_words = (uint32_t)(lists.size() * G);
@@ -1487,12 +1494,7 @@ bool build_node(HostTableSet& h, const std::vector<TableAnalysis*>& an, const st
     }
     if (X.empty()) X.resize(4, 0);
     if ((uint64_t)X.size() * 4u >= kMaxLoaderBytes || (uint64_t)img.size() * 4u >= kMaxLoaderBytes) {
-        h.node_img.clear();  // (the loaders' 32-bit byte offsets: no node; the per-table path)
-        h.node_aux.clear();
-        h.node_cross.clear();
-        h.node = DevNode{};
-        h.node_rec_words = 0;
-        return false;
+        return false;  // (the loaders' 32-bit byte offsets: no node; the per-table path)
     }
     if (std::getenv("PG_NODE_DEBUG"))  // measurement aid: the image's shape
         std::fprintf(stderr,
@@ -1503,6 +1505,16 @@ bool build_node(HostTableSet& h, const std::vector<TableAnalysis*>& an, const st
                      (N.lrec ? N.lrec : N.img_words) - N.img_words_base, N.lrec ? N.img_words - N.lrec : 0,
                      N.img_words);
     return true;
+}
+
+// A failed build leaves no node: every consumer takes a non-empty h.node_img for a complete
+// classifier (capi.cpp, device.hip), and build_node_image has exits behind its first write to it
+// -- the retries without the uniform layout included, which return through here too.
+bool build_node(HostTableSet& h, const std::vector<TableAnalysis*>& an, const std::vector<NodePod>& pods,
+                const NodePod& node_end, const Tuning& tu) {
+    if (build_node_image(h, an, pods, node_end, tu)) return true;
+    clear_node(h);
+    return false;
 }
 
 }  // namespace pg

@@ -304,6 +304,16 @@ class Engine:
                                             int(node) | (2 if pred else 0) | (4 if common else 0)))
         return (out, cnt) if counters else out
 
+    def debug_endpoint_probe(self, ips):
+        """TESTS ONLY: where the end-point hash table finds each address (pg_debug_endpoint_probe).
+        -> (probe steps u32 [n], start slot u32 [n], the table's capacity)"""
+        import numpy as np
+        ips = np.ascontiguousarray(ips, dtype=np.uint32)
+        steps, slot, cap = np.zeros(len(ips), np.uint32), np.zeros(len(ips), np.uint32), C.c_uint32()
+        p = lambda x: x.ctypes.data_as(C.c_void_p)
+        self._ck(lib.pg_debug_endpoint_probe(self.h, p(ips), len(ips), p(steps), p(slot), C.byref(cap)))
+        return steps, slot, cap.value
+
     def debug_reach_matrix_host(self, src_ips, dst_ips, services, words=True, node=True):
         """TESTS ONLY: pg_reach_matrix's code run on the host (pg_debug_reach_matrix_host).
         services: (protocol, src port, dst port). -> packed u32 [n_svc, n_src, row_words], and the
