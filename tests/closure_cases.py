@@ -19,6 +19,14 @@ prefilled output and assert that they stay untouched, and the expected packed wo
 Expected's product is an fp32 matrix product, or above 2500 nodes with a small frontier (the star) the OR
 of bit-packed rows.
 
+Past 4096 end points (edge_sizes: the plan's tile_cols of 4096 and of 2^15 end points at -1, 0, +1) the
+inputs are built without n x n codes. Islands(n): five islands of 48 nodes with about 3 random edges per
+node inside and a bridge from each to the next, every other node isolated, placed across the kernel's
+cuts (island_starts); its expected closure is Expected on the 240 island nodes scattered into n x n
+(Embedded), and check_walk_shape holds the reference alone to what makes the walk non-trivial.
+LargeMedium(n): 4 random edges per node; its closure is n^3 work per level and comes from the caller's
+reference. large_runs are the runs of such a graph, LARGE_WANT the references' numbers.
+
 The chain policy (chain(extra)): 12 local pods c0..c11 at 10.40.0.1 + k on tap k; out-tap k reflects
 TCP 80 from c(k-1), in-tap k reflects TCP 80 to c(k+1), both end in DENY; an extra edge (a, b) is a
 REFLECT of UDP 53 ahead of the DENYs of out-tap b and in-tap a. The graph is the path c0 -> .. -> c11
@@ -39,6 +47,7 @@ from vpp_amd._capi import lib
 ALLOW = 2
 SIZES = (1, 2, 15, 16, 17, 31, 32, 33, 64, 65, 100, 257)
 FAMILIES = ("empty", "full", "chain", "ring", "star", "two-cliques", "sparse", "medium", "dense")
+SEEDED = FAMILIES + ("islands",)   # (a family's place here goes into its generator's seed)
 FILL = 0xFFFFFFFF
 GUARD = 3   # prefilled words behind every output that must stay untouched
 
@@ -67,14 +76,43 @@ def edges(n, family, g):
             e[h - 1, h] = True
     elif family in ("sparse", "medium", "dense"):
         e = g.random((n, n)) < {"sparse": 1.5 / n, "medium": 4.0 / n, "dense": 0.5}[family]
+    elif family == "islands":
+        starts = island_starts(n)
+        for k, s in enumerate(starts):
+            e[s:s + ISLAND, s:s + ISLAND] = g.random((ISLAND, ISLAND)) < 3.0 / ISLAND
+            if k:
+                e[starts[k - 1] + ISLAND - 1, s] = True   # the bridge from the island before
     else:
         assert family == "empty", family
     return e
 
 
+ISLANDS, ISLAND = 5, 48
+
+
+def island_starts(n):
+    """where the islands of n nodes begin, ascending: at node 0, 24 nodes ahead of columns 2048, 4096 and
+    8192 (the cuts of the closure's chunks, lane widths and column tiles) where an island fits there in
+    front of the last one, and the last 48 nodes; an island that does not fit goes into the middle of
+    the widest gap, 8 columns behind a multiple of 32"""
+    assert n >= 2 * ISLANDS * ISLAND, n
+    last = n - ISLAND
+    starts = [0] + [c - ISLAND // 2 for c in (2048, 4096, 8192) if c + ISLAND // 2 <= last] + [last]
+    while len(starts) < ISLANDS:
+        gap, at = max((b - (a + ISLAND), a + ISLAND) for a, b in zip(starts, starts[1:]))
+        s = (at + (gap - ISLAND) // 2) // 32 * 32 + 8
+        assert at <= s and s + ISLAND <= at + gap, (n, starts)
+        starts = sorted(starts + [s])
+    return starts
+
+
+def island_nodes(n):
+    return np.concatenate([np.arange(s, s + ISLAND) for s in island_starts(n)])
+
+
 class Synthetic:
     def __init__(self, n, family, n_svc=3, seed=0):
-        g = np.random.default_rng([seed, n, FAMILIES.index(family), n_svc])
+        g = np.random.default_rng([seed, n, SEEDED.index(family), n_svc])
         self.n, self.n_svc, self.family = n, n_svc, family
         e = edges(n, family, g)
         owner = g.integers(0, n_svc, (n, n), dtype=np.uint8)
@@ -132,6 +170,160 @@ def product(front, a):
     for i in np.flatnonzero(front.any(axis=1)):
         out[i] = np.bitwise_or.reduce(bits[front[i]], axis=0)
     return np.unpackbits(out, axis=1, count=n).astype(bool)
+
+
+# ---- past 4096 end points ------------------------------------------------------------------------
+class Embedded:
+    """Expected's interface for a closure `sub` over the nodes `idx` of an n-node graph whose other
+    nodes are isolated: sub's matrices scattered into n x n ones"""
+
+    def __init__(self, sub, idx, n):
+        self.n, self.levels, self.idx = n, sub.levels, idx
+        self.edges = np.zeros((n, n), bool)
+        self.hops = np.zeros((n, n), np.uint16)
+        self.edges[np.ix_(idx, idx)] = sub.edges
+        self.hops[np.ix_(idx, idx)] = sub.hops
+
+    at = Expected.at
+
+
+class Islands(Synthetic):
+    """the family "islands" at n end points: every edge lies among the 240 island nodes, so the closure
+    of a selection is Expected on the 240-node subgraph (`sub`, its codes), embedded. Synthetic's inputs
+    without n x n codes: every edge in one random slice, the other cells random codes from {0, 1, 3}"""
+
+    def __init__(self, n, n_svc=3, seed=0):
+        g = np.random.default_rng([seed, n, SEEDED.index("islands"), n_svc])
+        self.n, self.n_svc, self.family, self.codes = n, n_svc, "islands", None
+        self.idx = idx = island_nodes(n)
+        e = edges(n, "islands", g)
+        assert e.sum() == e[np.ix_(idx, idx)].sum()
+        e = e[np.ix_(idx, idx)]
+        owner = g.integers(0, n_svc, e.shape, dtype=np.uint8)
+        # random words, their ALLOW cells (2) turned into 3; the island rows are then packed from codes
+        w = g.integers(0, 1 << 32, (n_svc, n, row_words(n)), dtype=np.uint64).astype(np.uint32)
+        w |= (w >> 1) & ~w & np.uint32(0x55555555)
+        rows = ((w[:, idx, :, None] >> (2 * np.arange(16, dtype=np.uint32))) & 3).reshape(n_svc, len(idx), -1)[:, :, :n].astype(np.uint8)
+        self.sub = np.where(e[None] & (owner[None] == np.arange(n_svc)[:, None, None]), np.uint8(ALLOW), rows[:, :, idx])
+        rows[:, :, idx] = self.sub
+        for v in range(n_svc):
+            w[v, idx] = dc.pack_wide(rows[v])
+        pad = np.uint32(0xFFFFFFFF >> (2 * (-n & 15)))   # the cells of a row's last word
+        allow = (w >> 1) & ~w & np.uint32(0x55555555)
+        allow[:, :, -1] &= pad
+        pop8 = np.unpackbits(np.arange(256, dtype=np.uint8)[:, None], axis=1).sum(axis=1)
+        assert int(pop8[allow.view(np.uint8)].sum()) == int((self.sub == ALLOW).sum()) == int(e.sum())   # no ALLOW elsewhere
+        self.words = np.stack([dc.garbage(w[v] & np.where(np.arange(row_words(n)) == row_words(n) - 1, pad, np.uint32(0xFFFFFFFF)),
+                                          n, seed + 1 + v) for v in range(n_svc)])
+        self._expected = {}
+
+    def expected(self, select=None):
+        if select not in self._expected:
+            self._expected[select] = Embedded(Expected(self.sub, select), self.idx, self.n)
+        return self._expected[select]
+
+
+class LargeMedium:
+    """the family "medium" at n end points without n x n codes: every edge in one random slice, the other
+    cells random codes from {0, 1, 3}, the padding random. Its closure takes n^3 work per level: the tests
+    get it from a reference of their own over edge_matrix(select)"""
+
+    def __init__(self, n, n_svc=3, seed=0, words=True):
+        g = np.random.default_rng([seed, n, SEEDED.index("medium"), n_svc])
+        self.n, self.n_svc, self.family = n, n_svc, "medium"
+        self.i, self.j = np.nonzero(edges(n, "medium", g))
+        self.owner = g.integers(0, n_svc, len(self.i))
+        if not words:   # (the graph alone)
+            return
+        w = g.integers(0, 1 << 32, (n_svc, n, row_words(n)), dtype=np.uint64).astype(np.uint32)
+        w |= (w >> 1) & ~w & np.uint32(0x55555555)   # (a random ALLOW becomes 3)
+        at, shift = (self.owner, self.i, self.j // 16), (2 * (self.j % 16)).astype(np.uint32)
+        np.bitwise_and.at(w, at, ~(np.uint32(3) << shift))
+        np.bitwise_or.at(w, at, np.uint32(ALLOW) << shift)
+        w[:, :, -1] &= np.uint32(0xFFFFFFFF >> (2 * (-n & 15)))
+        self.words = np.stack([dc.garbage(w[v], n, seed + 1 + v) for v in range(n_svc)])
+
+    def edge_matrix(self, select=None):
+        keep = np.ones(len(self.i), bool) if select is None else np.isin(self.owner, list(select))
+        e = np.zeros((self.n, self.n), bool)
+        e[self.i[keep], self.j[keep]] = True
+        return e
+
+
+def plan_shape(e, n):
+    """(lane_words, col_tiles) of the closure's plan for n end points, from what pg_debug_reach_closure_plan
+    gives: a column tile is 64 lanes of lane_words bit-words of 32 columns, the grid row tiles x column tiles"""
+    p = e.debug_reach_closure_plan(n)
+    assert p["tile_cols"] % 2048 == 0 and p["grid"] % -(-n // p["tile_rows"]) == 0, p
+    return p["tile_cols"] // 2048, p["grid"] // -(-n // p["tile_rows"])
+
+
+def edge_sizes(e):
+    """the column tiles of the plans of 4096 and of 2^15 end points, each at -1, 0 and +1: where a lane goes
+    from 2 to 4 bit-words, and where a second column of workgroups begins"""
+    return tuple(e.debug_reach_closure_plan(m)["tile_cols"] + d for m in (4096, 1 << 15) for d in (-1, 0, 1))
+
+
+EDGE_PLANS = ((2, 1), (2, 1), (4, 1), (4, 1), (4, 1), (4, 2))   # plan_shape at edge_sizes
+
+
+def large_runs(levels):
+    """(select, max_hops, out_hops, out_count) of the runs of a large closure test: all slices and one slice,
+    max_hops 0, 2 and levels - 1, one run without out_hops and one without out_count"""
+    return ((None, 0, True, True), ((1,), 0, True, True), (None, 2, True, True), (None, levels - 1, True, True),
+            (None, 0, False, True), ((1,), 2, True, False))
+
+
+LARGE_SEED = 21
+# the reference's (edges, reachable, levels) of the large graphs (n, family, seed), all slices, measured on
+# the CPU: the islands by Expected on their 240 nodes, medium by Expected's fp32 products
+LARGE_WANT = {(4095, "islands", 21): (737, 19463, 14), (4096, "islands", 21): (731, 30521, 24), (4097, "islands", 21): (720, 29971, 29),
+              (8191, "islands", 21): (684, 31069, 28), (8192, "islands", 21): (746, 30357, 26), (8193, "islands", 21): (684, 30319, 25),
+              (4097, "medium", 21): (16467, 16144251, 14), (8156, "medium", 21): (32737, 63991522, 15),
+              (8157, "medium", 21): (32779, 64120079, 14), (8192, "medium", 21): (33057, 64536943, 14),
+              (8193, "medium", 21): (32799, 64360456, 15)}
+
+
+def bit_words(rows):
+    """bool [k, n] -> the closure's bit-words u32 [k, ceil(n / 32)]: cell j at bit j % 32 of word j // 32"""
+    k, n = rows.shape
+    padded = np.zeros((k, -(-n // 32) * 32), bool)
+    padded[:, :n] = rows
+    return np.packbits(padded, axis=1, bitorder="little").view("<u4")
+
+
+def walk_shape(x, tile_rows=16):
+    """what a closure's level-wise walk looks like, from the expected hops alone: a dict of
+    levels; wide / narrow: frontier words (row, 32-column chunk, level) with >= 4 and with 1..3 bits;
+    gapped: (16-row tile, level) pairs that need two chunks with an unneeded one between them;
+    dead: the least share of row tiles without a frontier over the levels;
+    repeats: the share of the non-empty rows of the reach matrix with two equal adjacent non-zero bit-words"""
+    rows = np.flatnonzero(x.hops.any(axis=1))
+    tiles = -(-x.n // tile_rows)
+    out = {"levels": x.levels, "wide": 0, "narrow": 0, "gapped": 0, "dead": 1.0}
+    for level in range(1, x.levels + 1):
+        f = bit_words(x.hops[rows] == level)
+        bits = np.unpackbits(f.view(np.uint8), axis=1).reshape(len(rows), -1, 32).sum(axis=2)
+        out["wide"] += int((bits >= 4).sum())
+        out["narrow"] += int(((bits >= 1) & (bits <= 3)).sum())
+        live = set()
+        for t in np.unique(rows // tile_rows):
+            need = np.flatnonzero(np.bitwise_or.reduce(f[rows // tile_rows == t], axis=0))
+            if len(need):
+                live.add(int(t))
+                out["gapped"] += int(len(need) >= 2 and (np.diff(need) > 1).any())
+        out["dead"] = min(out["dead"], 1.0 - len(live) / tiles)
+    r = bit_words(x.hops[rows] > 0)
+    same = ((r[:, 1:] == r[:, :-1]) & (r[:, 1:] != 0)).any(axis=1)
+    out["repeats"] = float(same.mean()) if len(rows) else 0.0
+    return out
+
+
+def check_walk_shape(x):
+    """the preconditions of the large closure tests, on the reference alone: a star fails the last"""
+    w = walk_shape(x)
+    assert w["levels"] >= 6 and w["wide"] and w["narrow"] and w["gapped"] and w["dead"] > 0.9 and w["repeats"] < 0.1, w
+    return w
 
 
 def pack_reach(reach):

@@ -8,7 +8,13 @@ TREE_MAX_N nodes it builds, per src i, the predecessor vector
     ((h[i][:, None] == h[i][None, :] - 1) & edges).argmax(0),   pred = i where hops is 1
 (n^3 work over all srcs, 17 M at n = 257) and chases it for all queries at once, one numpy step per
 path position; for a larger graph it answers the queries' own steps, ((h[src] == t - 1) & (hT[cur] ==
-1)).argmax(1) over a block of queries. A step without a predecessor makes the query broken.
+1)).argmax(1) over a block of queries, or, when the queries come from at most FEW_SRCS srcs, those srcs'
+predecessor vectors built level by level (the same rule over the edges from level t - 1 to level t).
+A step without a predecessor makes the query broken.
+
+thresholds(e) finds the sizes at which the launch changes from pg_debug_reach_paths_plan alone;
+check_few_sources runs eight srcs against every dst of a large closure, analytic_queries are queries of
+the two cliques and the hub-last star whose paths are written down from the closed forms.
 
 valid(...) checks a run on its own against an edge matrix that does not come from the hops (the codes
 of a synthetic graph, the oracle's of an engine): p_0 = src, p_d = dst, d == hops, every step an edge,
@@ -19,6 +25,7 @@ Every run prefills its outputs (the nodes with NODES_FILL, which is not 0xFFFF) 
 behind each that must stay untouched.
 """
 import ctypes as C
+import functools
 
 import numpy as np
 
@@ -32,6 +39,7 @@ LEN_FILL = 0xDDDD
 VIA_FILL = 0xFFFFFFFF
 GUARD = 3
 TREE_MAX_N = 300
+FEW_SRCS = 16
 OUTPUTS = ((True, True), (True, False), (False, True), (False, False))   # (nodes, via)
 
 
@@ -46,9 +54,17 @@ class Expected:
         """the predecessor vector of src i, -1 where there is none"""
         if i not in self._pred:
             hi = self.h[i].astype(np.int32)
-            mask = (hi[:, None] == hi[None, :] - 1) & self.edges
-            p = mask.argmax(0)
-            p[~mask.any(0)] = -1
+            if self.n <= TREE_MAX_N:
+                mask = (hi[:, None] == hi[None, :] - 1) & self.edges
+                p = mask.argmax(0)
+                p[~mask.any(0)] = -1
+            else:   # the same rule level by level: the edges from level t - 1 to level t alone
+                p = np.full(self.n, -1, np.int64)
+                for t in range(2, int(hi.max()) + 1):
+                    ks, js = np.flatnonzero(hi == t - 1), np.flatnonzero(hi == t)
+                    if len(ks) and len(js):
+                        mask = self.edges[np.ix_(ks, js)]
+                        p[js] = np.where(mask.any(0), ks[mask.argmax(0)], -1)
             p[hi == 1] = i
             self._pred[i] = p
         return self._pred[i]
@@ -63,6 +79,12 @@ class Expected:
         """p_{t-1} of the queries (src, ..) that stand at cur = p_t, -1 where there is none"""
         if self.n <= TREE_MAX_N:
             return self.tree()[src, cur]
+        srcs = np.unique(src)
+        if len(srcs) <= FEW_SRCS:   # a large graph queried from a few srcs: their predecessor vectors
+            out = np.empty(len(src), np.int64)
+            for i in srcs:
+                out[src == i] = self.pred(int(i))[cur[src == i]]
+            return out
         if self._ht is None:
             self._ht = np.ascontiguousarray(self.h.T)
         out = np.empty(len(src), np.int64)
@@ -297,6 +319,102 @@ def boundary_queries(hops, seed=0):
     dd, P, _ = x.walk(src, dst)
     inner = (np.arange(P.shape[1])[None, :] >= 1) & (np.arange(P.shape[1])[None, :] < dd[:, None])
     return src.astype(np.uint32), dst.astype(np.uint32), int((inner & (P >= last)).any(axis=1).sum())
+
+
+# ---- the plan's thresholds -------------------------------------------------------------------------
+KIB48 = 48 * 1024   # the LDS a workgroup gets without asking for more
+
+
+@functools.lru_cache(maxsize=None)
+def thresholds(e):
+    """from pg_debug_reach_paths_plan alone, {"via_48k", "via_lds", "row_48k"}: lds_bytes grows with n but for
+    one drop, behind the last n whose out_via is counted in LDS (via_lds); via_48k is the last n up to there
+    whose workgroup stays within 48 KiB, row_48k the last n beyond whose staged row does"""
+    lds = np.array([e.debug_reach_paths_plan(n)["lds_bytes"] for n in range(1, (1 << 15) + 1)], np.int64)
+    drops = np.flatnonzero(np.diff(lds) < 0) + 1   # (lds[k] belongs to n = k + 1)
+    assert len(drops) == 1, drops
+    b = int(drops[0])
+    return {"via_48k": int(np.flatnonzero(lds[:b] <= KIB48).max()) + 1, "via_lds": b,
+            "row_48k": b + int(np.flatnonzero(lds[b:] <= KIB48).max()) + 1}
+
+
+THRESHOLDS = {"via_48k": 8156, "via_lds": 8192, "row_48k": 24472}   # today's
+
+
+def few_sources(n, seed=0, k=8, also=()):
+    """k srcs (node 0, node n - 1, one more of the last bit-word where it has one, those of `also`, the rest
+    random) against every dst -> (src, dst) sorted by src, and a permutation of the queries"""
+    g = np.random.default_rng([seed, n, k])
+    last = 32 * ((n - 1) // 32)
+    srcs = [0, n - 1, last + (n - 1 - last) // 2] + [int(i) for i in also]
+    for i in g.permutation(n - 2) + 1:
+        if len(set(srcs)) >= k:
+            break
+        srcs.append(int(i))
+    srcs = np.array(sorted(set(srcs)), np.uint32)
+    assert len(srcs) == k
+    return np.repeat(srcs, n), np.tile(np.arange(n, dtype=np.uint32), k), g.permutation(k * n)
+
+
+def check_few_sources(run, hops, edges, levels, outputs=False, one_block=None):
+    """`run` (run_host's contract without the engine) over few_sources of a large closure (hops, levels) with
+    the edge matrix it came from, one src a row of the greatest depth: sorted under max_len = levels, shuffled
+    under levels - 1 (some paths are then too long); with `outputs` every output combination; `one_block`: a
+    context manager under which the sorted set runs once more"""
+    n = hops.shape[0]
+    x = Expected(hops)
+    src, dst, perm = few_sources(n, also=[int(hops.max(axis=1).argmax())])
+    got = run(hops, n, src, dst, levels)
+    same(got, x, src, dst, levels, (n, "sorted"))
+    valid(got, edges, hops, src, dst, levels, (n, "sorted"))
+    res = got[3]
+    assert res["longest"] == levels >= 4 and res["n_too_long"] == 0 and res["n_via"] > 2 * res["n_found"], res
+    assert (got[2] > 0).sum() > 256, "the paths meet in a few hubs, as a star's do"
+    s, d = src[perm], dst[perm]
+    got = run(hops, n, s, d, levels - 1)
+    same(got, x, s, d, levels - 1, (n, "shuffled"))
+    valid(got, edges, hops, s, d, levels - 1, (n, "shuffled"))
+    assert got[3]["n_too_long"] > 0 and got[3]["n_via"] == res["n_via"] and (got[2] == x.outputs(src, dst, levels)[2]).all()
+    if outputs:
+        for nodes, via in OUTPUTS:
+            same(run(hops, n, s, d, levels - 1, nodes=nodes, via=via), x, s, d, levels - 1, (n, "outputs", nodes, via))
+    if one_block is not None:
+        with one_block:
+            same(run(hops, n, src, dst, levels), x, src, dst, levels, (n, "one workgroup per CU"))
+
+
+def analytic_queries(family, n):
+    """up to 64 queries of a two-cliques or hub-last graph of n >= 64 nodes with the path the least-predecessor
+    rule gives (None: no path), written down from the graphs' closed forms -> [(src, dst, path)]"""
+    last = 32 * ((n - 1) // 32)
+    if family == "hub-last":
+        hub = n - 1
+        q = [(i, j, [i, hub, j]) for i, j in ((0, 1), (1, 0), (5, 5), (0, n - 2), (n - 2, 0), (last, last), (n - 2, n - 2),
+                                              (n // 2, 7), (last, 3), (3, last))]
+        # every node is a predecessor of the hub: the least one is node 0
+        return q + [(hub, hub, [hub, 0, hub]), (hub, 4, [hub, 4]), (4, hub, [4, hub]), (0, hub, [0, hub]), (hub, 0, [hub, 0])]
+    assert family == "two-cliques" and n - last >= 3 and n >= 64, (family, n)
+    h = n // 2
+    q = [(i, j, [i, h - 1, h, j]) for i, j in ((0, n - 1), (5, n - 2), (h - 2, last), (1, h + 1), (h - 2, n - 1), (17, last + 1))]
+    q += [(h - 1, n - 1, [h - 1, h, n - 1]), (h - 1, h + 1, [h - 1, h, h + 1]), (0, h, [0, h - 1, h]), (h - 2, h, [h - 2, h - 1, h]),
+          (h - 1, h, [h - 1, h])]
+    # both ends in the last bit-word; a cycle goes through the least node of the clique
+    q += [(n - 1, n - 2, [n - 1, n - 2]), (last, n - 1, [last, n - 1]), (n - 1, n - 1, [n - 1, h, n - 1]), (last, last, [last, h, last]),
+          (h, h, [h, h + 1, h]), (0, 0, [0, 1, 0]), (3, 3, [3, 0, 3]), (h - 1, h - 1, [h - 1, 0, h - 1]), (2, 9, [2, 9])]
+    return q + [(n - 1, 0, None), (h, h - 1, None), (last, 5, None), (n - 1, h - 1, None), (h + 1, 0, None)]
+
+
+def check_analytic(got, n, queries, max_len):
+    """a run over analytic_queries (every path fits max_len) against the paths written down there"""
+    lens, rows, via, res = got
+    paths = [p for _, _, p in queries]
+    assert lens.tolist() == [len(p) - 1 if p else 0 for p in paths]
+    assert rows.tolist() == [(p or []) + [NONE] * (max_len + 1 - len(p or [])) for p in paths]
+    mids = [k for p in paths if p for k in p[1:-1]]
+    assert (via == np.bincount(mids, minlength=n)).all(), np.flatnonzero(via != np.bincount(mids, minlength=n))[:3].tolist()
+    found = [p for p in paths if p]
+    assert res == {"n_found": len(found), "n_unreachable": len(paths) - len(found), "n_too_long": 0, "n_broken": 0,
+                   "n_via": len(mids), "longest": max(len(p) - 1 for p in found)}, res
 
 
 def ring_hops(n):

@@ -53,6 +53,46 @@ def test_per_word_code():
     assert ((hops == 1) == (s.codes[0] == cc.ALLOW)).all() and (counts == (s.codes[0] == cc.ALLOW).sum(axis=1)).all()
 
 
+# ---- past 4096 end points ------------------------------------------------------------------------
+def test_island_placement():
+    """five disjoint islands inside the graph, one across every cut that lies far enough inside it, the last
+    ending at node n - 1"""
+    for n in cc.edge_sizes(engine()) + (480, 8300, 1 << 15):
+        s = cc.island_starts(n)
+        assert len(s) == cc.ISLANDS and s[0] == 0 and s[-1] == n - cc.ISLAND and all(b - a >= cc.ISLAND for a, b in zip(s, s[1:]))
+        for cut in (2048, 4096, 8192):
+            assert (cut + cc.ISLAND // 2 > n - cc.ISLAND) or any(a < cut < a + cc.ISLAND for a in s), (n, cut, s)
+    assert cc.island_starts(8193)[-1] + cc.ISLAND - 1 == 8192   # (the last island then reaches over the cut by itself)
+
+
+def test_edge_sizes():
+    """the sizes of the large closure tests and what the plan does there (closure_cases.EDGE_PLANS)"""
+    e = engine()
+    sizes = cc.edge_sizes(e)
+    assert sizes == (4095, 4096, 4097, 8191, 8192, 8193)
+    assert tuple(cc.plan_shape(e, n) for n in sizes) == cc.EDGE_PLANS
+    assert [cc.plan_shape(e, n)[0] for n in (2048, 2049)] == [1, 2]
+    # the pack kernel's second round: more than 256 input words in a row
+    assert [cc.row_words(n) > 256 for n in sizes] == [False, False, True, True, True, True]
+
+
+@pytest.mark.parametrize("k", range(6))
+def test_islands(k):
+    """the islands at the six sizes around the lane-width and column-tile cuts: the preconditions on the
+    reference alone, the committed numbers, and the host twin against the embedded 240-node closure"""
+    n = cc.edge_sizes(engine())[k]
+    s = cc.Islands(n, seed=cc.LARGE_SEED)
+    x = s.expected()
+    cc.check_walk_shape(x)
+    star = cc.Expected(np.where(cc.edges(300, "star", None), np.uint8(cc.ALLOW), np.uint8(0))[None])
+    assert cc.walk_shape(star)["repeats"] > 0.9   # (what the star cannot see)
+    r = x.at(0)[3]
+    assert (r["n_edges"], r["n_reachable"], r["levels"]) == cc.LARGE_WANT[n, "islands", cc.LARGE_SEED]
+    assert (s.words[:, :, -1] >> (2 * (n & 15))).any() or not n & 15, "no garbage in the padding"
+    for sel, hop_bound, hops, counts in cc.large_runs(x.levels):
+        cc.same(run(s.words, n, sel, hop_bound, hops=hops, counts=counts), s.expected(sel), hop_bound, (n, sel, hop_bound))
+
+
 # ---- the fixture change ------------------------------------------------------------------------
 def test_fixture_oracle_numbers():
     """the oracle alone: the numbers of the fixture graphs (closure_cases.FIXTURE_WANT)"""

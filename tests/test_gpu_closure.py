@@ -1,5 +1,7 @@
 """The reachability closure on the device: pg_reach_closure against numpy and, byte for byte, against the
-host twin over the graphs of tests/closure_cases.py, the sizes around the launch plan's tile, an input
+host twin over the graphs of tests/closure_cases.py, the sizes around the launch plan's tile, the islands
+and a random graph at the sizes where a lane goes to 4 bit-words and a second column tile begins (against
+a torch reference on the device, itself pinned to numpy), an input
 that is not 16-B aligned, a stream of its own over prefilled buffers, matrix -> closure -> diff chained on
 the device from two engines, and away from the counters.
 """
@@ -39,8 +41,9 @@ def u32(t):
     return t.cpu().numpy().view(np.uint32)
 
 
-def run_dev(e, mt, n, select=None, max_hops=0, hops=True, counts=True, stream=None):
-    """pg_reach_closure over prefilled outputs with guards; cc.run_host's contract on a device tensor"""
+def launch(e, mt, n, select, max_hops, hops, counts, stream=None):
+    """pg_reach_closure over prefilled outputs with guards -> (packed, hops, counts: the device buffers with
+    their guards, the result struct)"""
     rw = cc.row_words(n)
     n_svc = mt.numel() // (n * rw)
     st = stream or torch.cuda.current_stream()
@@ -55,7 +58,23 @@ def run_dev(e, mt, n, select=None, max_hops=0, hops=True, counts=True, stream=No
                                 cbuf.data_ptr() if counts else None, C.byref(res), C.c_void_p(st.cuda_stream))
     assert code == 0, lib.pg_last_error(e.h)
     # (the call has synchronised its stream: no wait here before the outputs are read)
+    return pbuf, hbuf, cbuf, res
+
+
+def run_dev(e, mt, n, select=None, max_hops=0, hops=True, counts=True, stream=None):
+    """launch() with every output on the host; cc.run_host's contract on a device tensor"""
+    pbuf, hbuf, cbuf, res = launch(e, mt, n, select, max_hops, hops, counts, stream)
     return cc.finish(n, u32(pbuf), hbuf.cpu().numpy().view(np.uint16), u32(cbuf), res, hops, counts)
+
+
+def run_big(e, mt, n, select=None, max_hops=0, hops=True, counts=True):
+    """run_dev() for a large graph: the hop counts stay on the device (int16 [n, n]), their guard and their
+    prefill are checked there; the packed words and the counts come to the host through cc.finish"""
+    pbuf, hbuf, cbuf, res = launch(e, mt, n, select, max_hops, hops, counts)
+    assert bool((hbuf[n * n:] == -1).all()), "a guard was written"
+    assert hops or bool((hbuf == -1).all())
+    packed, _, c, r = cc.finish(n, u32(pbuf), np.full(cc.GUARD, 0xFFFF, np.uint16), u32(cbuf), res, False, counts)
+    return packed, hbuf[:n * n].view(n, n) if hops else None, c, r
 
 
 def run(*args, **kw):
@@ -110,6 +129,136 @@ def test_two_column_tiles():
     x = s.expected()
     assert x.levels == 2 and x.at(0)[3]["n_reachable"] == n * n
     cc.same(run(dev(s.words), n, None, 0), x, 0, "star")
+
+
+# ---- past 4096 end points: a reference on the device that shares no code with the kernels ----------
+def dev_pack(reach):
+    """bool [n, n] on the device -> the closure's packed words on the host (u32 [n, row_words]): ALLOW where
+    reachable, padding zero; in blocks of rows, as sums of 16 cells times 2 * 4^k"""
+    n, rw = reach.shape[0], cc.row_words(reach.shape[0])
+    weight = torch.tensor([cc.ALLOW << (2 * k) for k in range(16)], dtype=torch.int64, device="cuda")
+    out = torch.empty((n, rw), dtype=torch.int64, device="cuda")
+    for r0 in range(0, n, 1024):
+        cells = torch.zeros((min(1024, n - r0), rw * 16), dtype=torch.int64, device="cuda")
+        cells[:, :n] = reach[r0:r0 + 1024]
+        out[r0:r0 + 1024] = (cells.view(-1, rw, 16) * weight).sum(dim=2)
+    return out.cpu().numpy().astype(np.uint32)
+
+
+class DevExpected:
+    """cc.Expected's answers from hop counts held on the device (int16 [n, n])"""
+
+    def __init__(self, hops):
+        self.hops, self.n, self.levels = hops, hops.shape[0], int(hops.max()) if hops.numel() else 0
+
+    @classmethod
+    def closure(cls, edges):
+        """the closure of a bool edge matrix on the device by level-wise boolean products, each an fp32
+        matrix product of 0/1 operands (sums <= n < 2^24: exact)"""
+        a = edges.float()
+        hops, reach, front = edges.to(torch.int16), edges.clone(), edges
+        level = int(edges.any())
+        while level:
+            front = ((front.float() @ a) > 0) & ~reach
+            if not bool(front.any()):
+                break
+            level += 1
+            hops.masked_fill_(front, level)
+            reach |= front
+        assert int(hops.max()) == level
+        return cls(hops)
+
+    @classmethod
+    def of(cls, hops):
+        """from a uint16 numpy matrix"""
+        return cls(torch.from_numpy(np.ascontiguousarray(hops).view(np.int16)).cuda())
+
+    def at(self, max_hops=0):
+        """(packed u32 on the host, hops int16 on the device, counts u32 on the host, result dict) under max_hops"""
+        hops = self.hops if not max_hops else torch.where(self.hops <= max_hops, self.hops, torch.zeros_like(self.hops))
+        reach = hops > 0
+        res = {"levels": int(hops.max()), "n_edges": int((self.hops == 1).sum()), "n_reachable": int(reach.sum())}
+        return dev_pack(reach), hops, reach.sum(dim=1).cpu().numpy().astype(np.uint32), res
+
+    def numbers(self):
+        r = self.at(0)[3]
+        return r["n_edges"], r["n_reachable"], r["levels"]
+
+
+def same_big(got, x, max_hops, what):
+    """cc.same() for run_big() against a DevExpected: the hop counts are compared on the device"""
+    packed, h, c, r = got
+    want_packed, want_hops, want_counts, res = x.at(max_hops)
+    assert r == res, (what, r, res)
+    assert (packed == want_packed).all(), (what, "packed", np.argwhere(packed != want_packed)[:3].tolist())
+    assert h is None or torch.equal(h, want_hops), (what, "hops", (h != want_hops).nonzero()[:3].tolist())
+    assert c is None or (c == want_counts).all(), (what, "counts", np.flatnonzero(c != want_counts)[:3].tolist())
+
+
+@pytest.mark.parametrize("family", ("medium", "two-cliques"))
+@pytest.mark.parametrize("n", (257, 2049))
+def test_device_reference(n, family):
+    """the device reference against cc.Expected, bit for bit: hops, and under max_hops 0, 2 and levels - 1 the
+    packed words, the counts and the result"""
+    s = cc.synthetic(n, family, n_svc=2, seed=3)
+    for sel in (None, (1,)):
+        x = s.expected(sel)
+        d = DevExpected.closure(torch.from_numpy(x.edges).cuda())
+        assert d.levels == x.levels and (d.hops.cpu().numpy().view(np.uint16) == x.hops).all(), (n, family, sel)
+        for k in (0, 2, max(1, x.levels - 1)):
+            reach, hops, counts, res = x.at(k)
+            packed, dh, dc_, dres = d.at(k)
+            assert dres == res and (packed == cc.pack_reach(reach)).all() and (dc_ == counts).all(), (n, family, sel, k)
+            assert (dh.cpu().numpy().view(np.uint16) == hops).all()
+        assert (DevExpected.of(x.hops).hops.cpu().numpy().view(np.uint16) == x.hops).all()
+
+
+def check_large(e, s, n, expected, host_twin):
+    """the runs of cc.large_runs over a large graph `s` against `expected(select)` -> DevExpected, and byte for
+    byte against the host twin"""
+    mt = dev(s.words)
+    for sel, k, hops, counts in cc.large_runs(expected(None).levels):
+        same_big(run_big(e, mt, n, sel, k, hops, counts), expected(sel), k, (s.family, n, sel, k, hops, counts))
+    if host_twin:
+        h, d = cc.run_host(e, s.words, n), run_big(e, mt, n)
+        assert h[3] == d[3] and h[0].tobytes() == d[0].tobytes() and h[2].tobytes() == d[2].tobytes(), (s.family, n)
+        assert torch.equal(d[1], torch.from_numpy(h[1].view(np.int16)).cuda()), (s.family, n, "hops")
+
+
+def test_edge_plans():
+    e = engine()
+    sizes = cc.edge_sizes(e)
+    assert tuple(cc.plan_shape(e, n) for n in sizes) == cc.EDGE_PLANS
+
+
+@pytest.mark.parametrize("k", range(6))
+def test_islands_at_plan_edges(k):
+    """the islands at tile_cols - 1, tile_cols and tile_cols + 1 of the plans of 4096 and of 2^15 end points:
+    lanes of 2 and of 4 bit-words, one and two column tiles, the pack kernel's second round"""
+    e = engine()
+    n = cc.edge_sizes(e)[k]
+    assert cc.plan_shape(e, n) == cc.EDGE_PLANS[k]
+    s = cc.Islands(n, seed=cc.LARGE_SEED)
+    cc.check_walk_shape(s.expected())
+    ref = DevExpected.closure(torch.from_numpy(s.expected().edges).cuda())
+    assert ref.numbers() == cc.LARGE_WANT[n, "islands", cc.LARGE_SEED]
+    assert torch.equal(ref.hops, DevExpected.of(s.expected().hops).hops)
+    del ref
+    expected = functools.lru_cache(maxsize=None)(lambda sel: DevExpected.of(s.expected(sel).hops))
+    check_large(e, s, n, expected, host_twin=True)
+
+
+@pytest.mark.parametrize("k", (2, 5))
+def test_medium_past_plan_edges(k):
+    """a random graph of 4 edges per node one past the two tile widths: every row tile alive, frontiers in
+    every chunk; the device reference reproduces the numbers the CPU reference gave"""
+    e = engine()
+    n = cc.edge_sizes(e)[k]
+    assert cc.plan_shape(e, n) == cc.EDGE_PLANS[k]
+    s = cc.LargeMedium(n, seed=cc.LARGE_SEED)
+    expected = functools.lru_cache(maxsize=None)(lambda sel: DevExpected.closure(torch.from_numpy(s.edge_matrix(sel)).cuda()))
+    assert expected(None).numbers() == cc.LARGE_WANT[n, "medium", cc.LARGE_SEED]
+    check_large(e, s, n, expected, host_twin=k == 2)
 
 
 def test_unaligned_input():

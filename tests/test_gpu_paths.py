@@ -1,7 +1,8 @@
 """The reachability paths on the device: pg_reach_paths against numpy and, byte for byte, against the host
 twin over the graphs of tests/closure_cases.py, the chunk boundaries under one workgroup per CU, the
 sizes around a 2048-column pass, the deep ring, a hops matrix that is not 16-B aligned, a stream of its
-own over prefilled buffers, every output combination, a broken matrix, 2^15 end points, matrix ->
+own over prefilled buffers, every output combination, a broken matrix, 2^15 end points, multi-hop paths
+at the sizes where out_via moves from LDS to global adds and where the LDS passes 48 KiB, matrix ->
 closure -> paths chained on the device from two engines, the wrappers, and away from the counters.
 """
 import ctypes as C
@@ -201,6 +202,78 @@ def test_32k_end_points():
     expect_via[0], expect_via[1] = 5, 1
     assert (via == expect_via).all()
     assert res == {"n_found": 8, "n_unreachable": 0, "n_too_long": 0, "n_broken": 0, "n_via": 6, "longest": 2}
+
+
+# ---- the plan's thresholds: where out_via is counted, and the LDS a workgroup asks for -------------
+@pytest.mark.parametrize("which, d", (("via_48k", 0), ("via_48k", 1), ("via_lds", 0), ("via_lds", 1)))
+def test_medium_at_thresholds(which, d):
+    """a random graph of 4 edges per node at the last size whose workgroup counts out_via within 48 KiB of
+    LDS and one past it (the launch then asks for more), at the last size that counts it in LDS at all and
+    one past it (adds to out_via itself): eight srcs against every dst over the device reference's
+    closure, paths of up to levels edges; at via_lds also under one workgroup per CU, which walks many
+    items and adds its LDS words once"""
+    from test_gpu_closure import DevExpected
+    e = engine()
+    t = pc.thresholds(e)
+    assert t == pc.THRESHOLDS
+    n = t[which] + d
+    edges = cc.LargeMedium(n, seed=cc.LARGE_SEED, words=False).edge_matrix()
+    ref = DevExpected.closure(torch.from_numpy(edges).cuda())
+    assert ref.numbers() == cc.LARGE_WANT[n, "medium", cc.LARGE_SEED]
+    hops = ref.hops.cpu().numpy().view(np.uint16)
+    levels = ref.levels
+    del ref
+    pc.check_few_sources(device_runner(), hops, edges, levels, outputs=which == "via_lds",
+                         one_block=e.tuning(blocks_per_cu=1) if (which, d) == ("via_lds", 0) else None)
+
+
+def dev_closed_form(family, n):
+    """the hops of two-cliques or hub-last built on the device from their closed forms (int16 [n, n])"""
+    if family == "hub-last":
+        h = torch.full((n, n), 2, dtype=torch.int16, device="cuda")
+        h[n - 1, :] = 1
+        h[:, n - 1] = 1
+        h[n - 1, n - 1] = 2
+        return h
+    assert family == "two-cliques"
+    k = n // 2   # nodes 0 .. k - 1 and k .. n - 1, the bridge k - 1 -> k
+    h = torch.zeros((n, n), dtype=torch.int16, device="cuda")
+    h[:k, :k] = 1
+    h[k:, k:] = 1
+    h.diagonal().fill_(2)
+    h[:k, k:] = 3
+    h[k - 1, k:] = 2
+    h[:k, k] = 2
+    h[k - 1, k] = 1
+    return h
+
+
+@pytest.mark.parametrize("family", ("two-cliques", "hub-last"))
+def test_closed_forms(family):
+    for n in (257, 300):
+        assert (dev_closed_form(family, n).cpu().numpy().view(np.uint16) == pc.boundary_graph(family, n)[0]).all(), (family, n)
+
+
+@pytest.mark.parametrize("family", ("two-cliques", "hub-last"))
+@pytest.mark.parametrize("size", ("row_48k", "row_48k + 1", "2^15"))
+def test_large_rows(size, family):
+    """the staged row alone at the last size within 48 KiB of LDS, one past it and past 64 KiB: paths of three
+    edges across the bridge, ends in the last bit-word, dst n - 1, the hub's least predecessor, no path"""
+    e = engine()
+    row = pc.thresholds(e)["row_48k"]
+    assert row == pc.THRESHOLDS["row_48k"]
+    n = {"row_48k": row, "row_48k + 1": row + 1, "2^15": 1 << 15}[size]
+    lds = e.debug_reach_paths_plan(n)["lds_bytes"]
+    assert (lds <= pc.KIB48, lds > 64 * 1024) == {"row_48k": (True, False), "row_48k + 1": (False, False), "2^15": (False, True)}[size]
+    try:
+        h = dev_closed_form(family, n)
+    except torch.cuda.OutOfMemoryError as err:
+        pytest.skip("no room for the hops matrix: %s" % err)
+    queries = pc.analytic_queries(family, n)
+    src, dst = np.array([(s, d) for s, d, _ in queries], np.uint32).T
+    pc.check_analytic(run_dev(e, h, n, src, dst, 3), n, queries, 3)
+    got = run_dev(e, h, n, src[::-1], dst[::-1], 3, via=False)
+    assert got[0].tolist() == [len(p) - 1 if p else 0 for _, _, p in queries[::-1]] and got[2] is None
 
 
 # ---- matrix -> closure -> paths on the device, inputs from two engines --------------------------

@@ -60,6 +60,72 @@ def test_pass_boundary(family, n):
     pc.valid(got, edges, h, src, dst, 4, (family, n))
 
 
+# ---- past 4096 end points --------------------------------------------------------------------------
+def test_reference_routes(monkeypatch):
+    """Expected's routes for a large graph give what the n^2 masks give: the level-wise predecessor vector,
+    and a step answered from a few srcs' vectors"""
+    for n, family in ((257, "medium"), (200, "sparse"), (64, "two-cliques")):
+        h = cc.synthetic(n, family).expected().hops
+        want = pc.Expected(h).tree()
+        monkeypatch.setattr(pc, "TREE_MAX_N", 0)
+        x = pc.Expected(h)
+        assert (np.stack([x.pred(i) for i in range(n)]) == want).all(), (n, family)
+        src, dst, perm = pc.few_sources(n)
+        few = x.outputs(src[perm], dst[perm], n)
+        monkeypatch.setattr(pc, "FEW_SRCS", 0)
+        many = pc.Expected(h).outputs(src[perm], dst[perm], n)
+        monkeypatch.undo()
+        tree = pc.Expected(h).outputs(src[perm], dst[perm], n)
+        for a, b, c in zip(few, many, tree):
+            assert (a == b).all() and (a == c).all() if isinstance(a, np.ndarray) else a == b == c, (n, family)
+
+
+def test_thresholds():
+    """the sizes of the large path tests, found from the plan: the last workgroup within 48 KiB that counts
+    out_via in LDS, the last that counts it in LDS at all, the last row that fits 48 KiB alone"""
+    e = engine()
+    t = pc.thresholds(e)
+    assert t == pc.THRESHOLDS
+    lds = lambda n: e.debug_reach_paths_plan(n)["lds_bytes"]
+    assert lds(t["via_48k"]) <= pc.KIB48 < lds(t["via_48k"] + 1) and lds(t["via_lds"]) > pc.KIB48 > lds(t["via_lds"] + 1)
+    assert lds(t["row_48k"]) <= pc.KIB48 < lds(t["row_48k"] + 1) and lds(1 << 15) > 64 * 1024
+
+
+def test_few_sources():
+    for n in (257, 8193, 8156):
+        src, dst, perm = pc.few_sources(n)
+        srcs = np.unique(src)
+        last = 32 * ((n - 1) // 32)
+        assert len(srcs) == 8 and srcs[0] == 0 and srcs[-1] == n - 1 and (srcs >= last).sum() >= min(2, n - last)
+        assert len(src) == 8 * n and (np.sort(perm) == np.arange(8 * n)).all() and (dst.reshape(8, n) == np.arange(n)).all()
+
+
+@pytest.mark.parametrize("family", ("two-cliques", "hub-last"))
+def test_analytic_queries(family):
+    """the paths written down in paths_cases.analytic_queries are Expected's, and the host twin's"""
+    for n in (300, 2100):
+        h, edges = pc.boundary_graph(family, n)
+        queries = pc.analytic_queries(family, n)
+        src, dst = np.array([(s, d) for s, d, _ in queries], np.uint32).T
+        assert len(queries) <= 64 and max(len(p) for _, _, p in queries if p) == (4 if family == "two-cliques" else 3)
+        got = run(h, n, src, dst, 3)
+        pc.check_analytic(got, n, queries, 3)
+        pc.same(got, pc.Expected(h), src, dst, 3, (family, n))
+        pc.valid(got, edges, h, src, dst, 3, (family, n))
+
+
+def test_medium_at_via_threshold():
+    """a random graph of 4 edges per node at the last size whose workgroup counts out_via within 48 KiB of
+    LDS: eight srcs against every dst over the CPU reference's closure, paths of up to levels edges"""
+    n = pc.THRESHOLDS["via_48k"]
+    g = cc.LargeMedium(n, seed=cc.LARGE_SEED, words=False)
+    edges = g.edge_matrix()
+    cx = cc.Expected(np.where(edges, np.uint8(cc.ALLOW), np.uint8(0))[None])
+    r = cx.at(0)[3]
+    assert (r["n_edges"], r["n_reachable"], r["levels"]) == cc.LARGE_WANT[n, "medium", cc.LARGE_SEED]
+    pc.check_few_sources(run, cx.hops, edges, cx.levels)
+
+
 def test_ring_depth():
     """the analytic ring at n = 2049: 2048 and 2049 edges, and all three too long for max_len 64"""
     pc.check_ring(run)
