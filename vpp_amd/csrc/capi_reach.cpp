@@ -44,8 +44,8 @@ struct HostHoist {
     std::vector<W2> g;
     // spec: src_ip, dst_ip, n_src, n_dst. -> the form's end-point arrays
     template <class SPEC>
-    ReachEnds run(bool uni, const DevTableSet& T, const SPEC& spec, const std::vector<W4>& svc,
-                  const std::vector<uint32_t>& list) {
+    ReachEnds run(bool uni, const DevTableSet& T, const SPEC& spec, const std::vector<W4>& svc, const uint32_t* list,
+                  uint32_t n_list) {
         const uint32_t ns = (uint32_t)spec.n_src, nd = (uint32_t)spec.n_dst;
         const DevLoader img{T.node.img};
         rec.resize(ns + nd), cls.resize(ns + nd), g.resize(svc.size());
@@ -54,7 +54,7 @@ struct HostHoist {
             if (uni) reach_end_uni(T.node, img, ip, &rec[e], &cls[e]);
             else rec[e] = reach_end_tab(T, ip);
         }
-        for (uint32_t v : list) g[v] = uni ? reach_svc_uni(T.node, img, svc[v]) : reach_svc_tab(svc[v]);
+        for (uint32_t k = 0; k < n_list; k++) g[list[k]] = uni ? reach_svc_uni(T.node, img, svc[list[k]]) : reach_svc_tab(svc[list[k]]);
         const uint32_t* c = uni ? cls.data() : nullptr;
         return ReachEnds{rec.data(), rec.data() + ns, c, uni ? c + ns : nullptr, ns, nd};
     }
@@ -125,18 +125,19 @@ int pg_debug_reach_matrix_host(pg_ctx* ctx, const pg_reach_spec* spec, uint32_t*
     const uint32_t nv = (uint32_t)spec->n_svc;
     const std::vector<W4> svc = reach_services(spec);
     const bool form_a = (flags & 1) && reach_form_a(T.node, E.tune);
-    std::vector<uint32_t> la, lb;  // the services of each form
-    for (uint32_t v = 0; v < nv; v++) (form_a && svc[v].x <= 2u ? la : lb).push_back(v);
+    std::vector<uint32_t> list;
+    const uint32_t na = reach_form_split(form_a, svc.data(), nv, nullptr, &list), nb = nv - na;
+    const uint32_t *la = list.data(), *lb = la + na;
     HostHoist H;
-    if (!la.empty()) {
-        const ReachEnds ends = H.run(true, T, *spec, svc, la);
-        const ReachPass P{ends, H.g.data(), la.data(), (uint32_t)la.size(), out_packed, out_words};
+    if (na) {
+        const ReachEnds ends = H.run(true, T, *spec, svc, la, na);
+        const ReachPass P{ends, H.g.data(), la, na, out_packed, out_words};
         if (T.node.wide) host_reach_pairs<true, true>(T, P);
         else host_reach_pairs<true, false>(T, P);
     }
-    if (!lb.empty()) {
-        const ReachEnds ends = H.run(false, T, *spec, svc, lb);
-        const ReachPass P{ends, H.g.data(), lb.data(), (uint32_t)lb.size(), out_packed, out_words};
+    if (nb) {
+        const ReachEnds ends = H.run(false, T, *spec, svc, lb, nb);
+        const ReachPass P{ends, H.g.data(), lb, nb, out_packed, out_words};
         host_reach_pairs<false, false>(T, P);
     }
     return PG_OK;
@@ -293,23 +294,23 @@ int pg_debug_reach_rules_host(pg_ctx* ctx, const pg_reach_rules_spec* spec, uint
     const DevTableSet T = host_view(E.host);
     const uint32_t nv = (uint32_t)spec->n_svc;
     const bool form_a = (flags & 1) && reach_form_a(T.node, E.tune);
-    std::vector<uint32_t> la, lb;  // the services of each form that weigh anything
-    for (uint32_t v = 0; v < nv; v++)
-        if (c.weight[v]) (form_a && c.svc[v].x <= 2u ? la : lb).push_back(v);
+    std::vector<uint32_t> list;  // (the services that weigh anything)
+    const uint32_t na = reach_form_split(form_a, c.svc.data(), nv, c.weight.data(), &list), nb = (uint32_t)list.size() - na;
+    const uint32_t *la = list.data(), *lb = la + na;
     const RulesPlan plan = rules_plan(c.n_slots, c.n_slots - c.n_rule_slots, out_evals != nullptr, out_cells != nullptr,
                                       E.tune.rules_hist_cells, c.max_weight);
     const RulesArgs A{c.weight.data(), reinterpret_cast<unsigned long long*>(out_evals),
                       reinterpret_cast<unsigned long long*>(out_cells), plan.evals, plan.cells, c.n_slots, plan.flush_words};
     HostHoist H;
     bool wrapped = false;
-    if (!la.empty()) {
-        const ReachEnds ends = H.run(true, T, c.reach, c.svc, la);
-        const ReachPass P{ends, H.g.data(), la.data(), (uint32_t)la.size(), nullptr, nullptr};
+    if (na) {
+        const ReachEnds ends = H.run(true, T, c.reach, c.svc, la, na);
+        const ReachPass P{ends, H.g.data(), la, na, nullptr, nullptr};
         wrapped |= T.node.wide ? host_rules_form<true, true>(T, P, A) : host_rules_form<true, false>(T, P, A);
     }
-    if (!lb.empty()) {
-        const ReachEnds ends = H.run(false, T, c.reach, c.svc, lb);
-        const ReachPass P{ends, H.g.data(), lb.data(), (uint32_t)lb.size(), nullptr, nullptr};
+    if (nb) {
+        const ReachEnds ends = H.run(false, T, c.reach, c.svc, lb, nb);
+        const ReachPass P{ends, H.g.data(), lb, nb, nullptr, nullptr};
         wrapped |= host_rules_form<false, false>(T, P, A);
     }
     if (wrapped) return fail(ctx, PG_EFAULT, "a 32-bit window cell wrapped between two flushes");
@@ -463,7 +464,7 @@ int pg_debug_reach_ports_host(pg_ctx* ctx, const pg_port_sweep_spec* spec, uint3
         len[k] = ports_len(lo.data(), K, k);
     }
     HostHoist H;
-    const ReachEnds ends = H.run(form_a, T, *spec, svc, list);
+    const ReachEnds ends = H.run(form_a, T, *spec, svc, list.data(), K);
     if (!form_a) host_ports_pairs<false, false>(T, ends, H.g.data(), len.data(), K, out_codes, out_open, out_words);
     else if (T.node.wide) host_ports_pairs<true, true>(T, ends, H.g.data(), len.data(), K, out_codes, out_open, out_words);
     else host_ports_pairs<true, false>(T, ends, H.g.data(), len.data(), K, out_codes, out_open, out_words);

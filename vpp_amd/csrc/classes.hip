@@ -27,8 +27,8 @@
 #include <algorithm>
 #include <string>
 
+#include "audit_launch.hpp"
 #include "classes.hpp"
-#include "hiputil.hpp"
 
 namespace pg {
 
@@ -165,8 +165,6 @@ __global__ __launch_bounds__(kClassesBlock) void k_classes_quotient(const uint32
     }
 }
 
-size_t up16(size_t n) { return (n + 15u) & ~(size_t)15u; }
-
 }  // namespace
 
 int dev_reach_classes(uint32_t blocks_per_cu, const ClassesSpecDev& spec, const ClassesOutDev& out, ClassesResult* result,
@@ -188,27 +186,25 @@ int dev_reach_classes(uint32_t blocks_per_cu, const ClassesSpecDev& spec, const 
     std::vector<uint32_t> aux, marks;
     ClassesSide src, dst;
     Scratch blk;
-    // one block: [signatures u64 | pairs or leaders u32 | marks u32 | src reps | dst reps], each padded to 16 B
+    // AUX: the src check's pairs or the dst check's leaders; SREP / DREP: the quotient's representatives or nothing
+    enum { SIG, AUX, MARKS, SREP, DREP };
     const size_t n_aux = std::max<size_t>(want_src ? 2u * (size_t)n_src : 0u, want_dst ? 16u * (size_t)rw : 0u);
     const size_t n_marks = std::max<size_t>(want_src ? n_src : 0u, want_dst ? 16u * (size_t)rw : 0u);
-    const size_t off_aux = up16(sig.size() * sizeof(uint64_t)), off_marks = off_aux + up16(n_aux * sizeof(uint32_t));
-    const size_t off_srep = off_marks + up16(n_marks * sizeof(uint32_t));
-    const size_t off_drep = off_srep + up16(out.quotient ? n_src * sizeof(uint32_t) : 0u);
-    const size_t total = off_drep + (out.quotient ? 16u * (size_t)rw * sizeof(uint32_t) : 0u);  // (whole words of 16)
-    if (Scratch::make(&blk, total, err) != 0) {
+    const auto l = lay_out({sig.size() * sizeof(uint64_t), n_aux * sizeof(uint32_t), n_marks * sizeof(uint32_t),
+                            out.quotient ? n_src * sizeof(uint32_t) : 0u, out.quotient ? 16u * (size_t)rw * sizeof(uint32_t) : 0u});
+    if (Scratch::make(&blk, l.total, err) != 0) {
         (void)hipGetLastError();
         return -2;
     }
-    unsigned long long* d_sig = blk.at<unsigned long long>(0);
-    uint32_t* d_aux = blk.at<uint32_t>(off_aux);
-    uint32_t* d_marks = blk.at<uint32_t>(off_marks);
+    unsigned long long* d_sig = l.at<unsigned long long>(blk, SIG);
+    uint32_t *d_aux = l.at<uint32_t>(blk, AUX), *d_marks = l.at<uint32_t>(blk, MARKS);
+    uint32_t *d_srep = l.at<uint32_t>(blk, SREP), *d_drep = l.at<uint32_t>(blk, DREP);
 
     // the grid of a column kernel and the run of each of its workgroups
     auto column_grid = [&](auto kernel, ClassesShape& S) {
-        const int grid = grid_resident(kernel, (int)kClassesBlock, 0, S.items * kClassesBlock, blocks_per_cu);
-        (void)hipGetLastError();  // (a failed occupancy query is answered by grid_resident's fall-back)
-        S.per = (S.items + (uint64_t)grid - 1) / (uint64_t)grid;
-        return (uint32_t)((S.items + S.per - 1) / S.per);
+        const Runs runs = run_grid(kernel, (int)kClassesBlock, 0, S.items, blocks_per_cu);
+        S.per = runs.per;
+        return (uint32_t)runs.groups;
     };
     auto wave_grid = [&](auto kernel, uint64_t n) {
         const int grid = grid_resident(kernel, (int)kClassesBlock, 0, n * kClassesWave, blocks_per_cu);
@@ -269,11 +265,11 @@ int dev_reach_classes(uint32_t blocks_per_cu, const ClassesSpecDev& spec, const 
     if (want_dst && (put(out.dst_class, dst.cls) || put(out.dst_rep, dst.rep))) return -1;
     if (out.quotient) {
         const uint32_t n_sc = (uint32_t)src.rep.size(), n_dc = (uint32_t)dst.rep.size();
-        if (put(blk.at<uint32_t>(off_srep), src.rep) || put(blk.at<uint32_t>(off_drep), dst.rep)) return -1;
+        if (put(d_srep, src.rep) || put(d_drep, dst.rep)) return -1;
         const uint64_t n_words = (uint64_t)spec.n_svc * n_sc * ((n_dc + 15u) / 16u);
         const uint32_t g = (uint32_t)std::min<uint64_t>((n_words + kClassesBlock - 1) / kClassesBlock, 4096);
-        hipLaunchKernelGGL(k_classes_quotient, dim3(g), dim3(kClassesBlock), 0, st, spec.matrix, n_src, rw,
-                           blk.at<uint32_t>(off_srep), n_sc, blk.at<uint32_t>(off_drep), n_dc, n_words, out.quotient);
+        hipLaunchKernelGGL(k_classes_quotient, dim3(g), dim3(kClassesBlock), 0, st, spec.matrix, n_src, rw, d_srep,
+                           n_sc, d_drep, n_dc, n_words, out.quotient);
         HIPCHK(hipGetLastError());
     }
     *result = ClassesResult{(uint32_t)src.rep.size(), (uint32_t)dst.rep.size(), std::max(src.rounds, dst.rounds)};

@@ -29,8 +29,8 @@
 #include <algorithm>
 #include <string>
 
+#include "audit_launch.hpp"
 #include "closure.hpp"
-#include "hiputil.hpp"
 
 namespace pg {
 
@@ -317,21 +317,22 @@ int dev_reach_closure(const ClosureSpecDev& spec, uint32_t* out_packed, uint16_t
     hipStream_t st = (hipStream_t)stream;
     const uint32_t n = spec.n, stride = closure_stride(n);
     const ClosurePlan p = closure_plan(n);
-    // one scratch block: [total u64, pad | A | R | F | F' | T | T' | live | live' | slice list], every
-    // part a multiple of 16 B
-    const size_t mat = (size_t)n * stride, tiles = (size_t)p.row_tiles * stride, flags = ((size_t)n + 3) & ~(size_t)3;
-    const size_t words = 4 + 4 * mat + 2 * tiles + 2 * flags + spec.n_list;
+    // TOTAL: the running popcount, a u64 cleared as 16 B; FN / TN / LIVE_N: the next level's F / T / live
+    enum { TOTAL, MAT_A, MAT_R, MAT_F, MAT_FN, TILE_T, TILE_TN, LIVE, LIVE_N, LIST };
+    const size_t mat = (size_t)n * stride * sizeof(uint32_t), tiles = (size_t)p.row_tiles * stride * sizeof(uint32_t);
+    const size_t flags = (((size_t)n + 3) & ~(size_t)3) * sizeof(uint32_t);  // (cleared whole)
+    const auto l = lay_out({16, mat, mat, mat, mat, tiles, tiles, flags, flags, spec.n_list * sizeof(uint32_t)});
     Scratch blk;
-    if (Scratch::make(&blk, words * sizeof(uint32_t), err) != 0) {
+    if (Scratch::make(&blk, l.total, err) != 0) {
         (void)hipGetLastError();
         return -2;
     }
-    unsigned long long* total = blk.at<unsigned long long>(0);
-    uint32_t* A = blk.at<uint32_t>(16);
-    uint32_t *R = A + mat, *F = R + mat, *Fn = F + mat, *T = Fn + mat, *Tn = T + tiles, *live = Tn + tiles,
-             *live_n = live + flags, *list = live_n + flags;
+    unsigned long long* total = l.at<unsigned long long>(blk, TOTAL);
+    uint32_t *A = l.at<uint32_t>(blk, MAT_A), *R = l.at<uint32_t>(blk, MAT_R), *F = l.at<uint32_t>(blk, MAT_F),
+             *Fn = l.at<uint32_t>(blk, MAT_FN), *T = l.at<uint32_t>(blk, TILE_T), *Tn = l.at<uint32_t>(blk, TILE_TN),
+             *live = l.at<uint32_t>(blk, LIVE), *live_n = l.at<uint32_t>(blk, LIVE_N), *list = l.at<uint32_t>(blk, LIST);
     HIPCHK(hipMemsetAsync(total, 0, 16, st));
-    HIPCHK(hipMemsetAsync(live, 0, flags * sizeof(uint32_t), st));
+    HIPCHK(hipMemsetAsync(live, 0, flags, st));
     if (spec.n_list) HIPCHK(hipMemcpyAsync(list, spec.svc_list, spec.n_list * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     if (out_hops) HIPCHK(hipMemsetAsync(out_hops, 0, (size_t)n * n * sizeof(uint16_t), st));
     const dim3 eg((stride + kEdgeWords - 1) / kEdgeWords, p.row_tiles);
@@ -349,7 +350,7 @@ int dev_reach_closure(const ClosureSpecDev& spec, uint32_t* out_packed, uint16_t
     uint32_t level = reached ? 1u : 0u;
     // (a shortest path has at most n edges: the loop ends by itself)
     for (uint64_t fresh = reached; fresh && (!spec.max_hops || level < spec.max_hops);) {
-        HIPCHK(hipMemsetAsync(live_n, 0, flags * sizeof(uint32_t), st));
+        HIPCHK(hipMemsetAsync(live_n, 0, flags, st));
         const StepArgs a{A, F, T, live, R, Fn, Tn, live_n, out_hops, total, n, stride, level + 1u};
         if (p.lane_words == 1) launch_step<1>(p, st, a);
         else if (p.lane_words == 2) launch_step<2>(p, st, a);

@@ -22,8 +22,8 @@
 #include <algorithm>
 #include <string>
 
+#include "audit_launch.hpp"
 #include "groups.hpp"
-#include "hiputil.hpp"
 
 namespace pg {
 
@@ -129,29 +129,23 @@ int dev_reach_groups(uint32_t blocks_per_cu, const GroupsSpecDev& spec, uint64_t
     S.items = (uint64_t)spec.n_svc * S.n_chunks * S.tiles;
     std::vector<unsigned char> host;  // (before blk: a call that leaves early still outlives the copy out of it)
     Scratch blk;
-    // one host block, one copy: [dst ids u16 x 16 row_words | chunks | rows], the first two padded to 16 B
-    const size_t off_chunks = (P.dgrp.size() * sizeof(uint16_t) + 15u) & ~(size_t)15u;
-    const size_t off_rows = (off_chunks + P.chunks.size() * sizeof(GroupsChunk) + 15u) & ~(size_t)15u;
-    const size_t total = off_rows + P.rows.size() * sizeof(uint32_t);
+    // the whole block is one host image and one copy; DGRP: the dst ids, u16 x 16 row_words
+    enum { DGRP, CHUNKS, ROWS };
+    const auto l =
+        lay_out({P.dgrp.size() * sizeof(uint16_t), P.chunks.size() * sizeof(GroupsChunk), P.rows.size() * sizeof(uint32_t)});
     if (S.items) {
-        host.assign(total, 0);
-        std::copy_n(reinterpret_cast<const unsigned char*>(P.dgrp.data()), P.dgrp.size() * sizeof(uint16_t), host.data());
-        std::copy_n(reinterpret_cast<const unsigned char*>(P.chunks.data()), P.chunks.size() * sizeof(GroupsChunk),
-                    host.data() + off_chunks);
-        std::copy_n(reinterpret_cast<const unsigned char*>(P.rows.data()), P.rows.size() * sizeof(uint32_t),
-                    host.data() + off_rows);
-        if (Scratch::make(&blk, total, err) != 0) {
+        host.assign(l.total, 0);
+        l.put(host, DGRP, DGRP, P.dgrp), l.put(host, DGRP, CHUNKS, P.chunks), l.put(host, DGRP, ROWS, P.rows);
+        if (Scratch::make(&blk, l.total, err) != 0) {
             (void)hipGetLastError();
             return -2;
         }
-        HIPCHK(hipMemcpyAsync(blk.at<unsigned char>(0), host.data(), total, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(blk.at<unsigned char>(0), host.data(), l.total, hipMemcpyHostToDevice, st));
         const size_t lds = (size_t)spec.n_dst_groups * 4u * sizeof(uint32_t);
-        const int grid = grid_resident(k_groups_count, (int)kGroupsBlock, lds, S.items * kGroupsBlock, blocks_per_cu);
-        (void)hipGetLastError();  // (a failed occupancy query is answered by grid_resident's fall-back)
-        S.per = (S.items + (uint64_t)grid - 1) / (uint64_t)grid;
-        const uint32_t g = (uint32_t)((S.items + S.per - 1) / S.per);
-        hipLaunchKernelGGL(k_groups_count, dim3(g), dim3(kGroupsBlock), lds, st, spec.matrix, S, blk.at<uint32_t>(off_rows),
-                           blk.at<GroupsChunk>(off_chunks), blk.at<uint16_t>(0),
+        const Runs runs = run_grid(k_groups_count, (int)kGroupsBlock, lds, S.items, blocks_per_cu);
+        S.per = runs.per;
+        hipLaunchKernelGGL(k_groups_count, dim3((uint32_t)runs.groups), dim3(kGroupsBlock), lds, st, spec.matrix, S,
+                           l.at<uint32_t>(blk, ROWS), l.at<GroupsChunk>(blk, CHUNKS), l.at<uint16_t>(blk, DGRP),
                            reinterpret_cast<unsigned long long*>(out_counts));
         HIPCHK(hipGetLastError());
     }

@@ -30,7 +30,7 @@
 #include <algorithm>
 #include <string>
 
-#include "hiputil.hpp"
+#include "audit_launch.hpp"
 #include "paths.hpp"
 
 namespace pg {
@@ -182,14 +182,11 @@ int launch_walk(uint32_t blocks_per_cu, PathsShape S, uint32_t lds, hipStream_t 
                 uint32_t* out_via, unsigned long long* result, std::string* err) {
     auto kernel = k_paths_walk<NODES, VIA>;
     // (a row of 2^15 cells and its 16 B pass 64 KiB of LDS)
-    if (lds > 48u * 1024u)
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int grid = grid_resident(kernel, (int)kPathsBlock, lds, (uint64_t)S.n_items * kPathsBlock, blocks_per_cu);
-    (void)hipGetLastError();  // (a failed occupancy query is answered by grid_resident's fall-back)
-    S.per = (S.n_items + (uint32_t)grid - 1u) / (uint32_t)grid;
-    const uint32_t g = (S.n_items + S.per - 1u) / S.per;
-    hipLaunchKernelGGL(kernel, dim3(g), dim3(kPathsBlock), lds, st, hops, ET, S, items, dst, pos, out_len, out_nodes, out_via,
-                       result);
+    HIPCHK(allow_dynamic_lds(kernel, lds));
+    const Runs runs = run_grid(kernel, (int)kPathsBlock, lds, S.n_items, blocks_per_cu);
+    S.per = (uint32_t)runs.per;
+    hipLaunchKernelGGL(kernel, dim3((uint32_t)runs.groups), dim3(kPathsBlock), lds, st, hops, ET, S, items, dst, pos, out_len,
+                       out_nodes, out_via, result);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -209,34 +206,31 @@ int dev_reach_paths(uint32_t blocks_per_cu, const PathsSpecDev& spec, uint16_t* 
     const PathsPartition& P = *spec.part;
     const PathsPlan plan = paths_plan(n);
     const uint32_t nq = (uint32_t)spec.n_queries, n_items = (uint32_t)P.items.size();
-    // one scratch block: [result 6 u64, pad | ET n x stride | dst | pos | items], every part a multiple
-    // of 16 B; the last three are one host block and one copy
-    auto pad16 = [](size_t b) { return (b + 15u) & ~(size_t)15u; };
-    const size_t off_et = 64, off_dst = off_et + (size_t)n * stride * sizeof(uint32_t);
-    const size_t off_pos = off_dst + pad16((size_t)nq * sizeof(uint32_t)), off_items = off_pos + pad16((size_t)nq * sizeof(uint32_t));
-    const size_t total = off_items + (size_t)n_items * sizeof(PathsItem);
-    std::vector<unsigned char> host(total - off_dst, 0);  // (before blk: a call that leaves early still outlives the copy out of it)
-    std::copy_n(reinterpret_cast<const unsigned char*>(P.dst.data()), (size_t)nq * sizeof(uint32_t), host.data());
-    std::copy_n(reinterpret_cast<const unsigned char*>(P.pos.data()), (size_t)nq * sizeof(uint32_t), host.data() + (off_pos - off_dst));
-    std::copy_n(reinterpret_cast<const unsigned char*>(P.items.data()), (size_t)n_items * sizeof(PathsItem),
-                host.data() + (off_items - off_dst));
+    // RESULT: kPathsResultWords u64 in 64 B, cleared whole; ET: n x stride; the last three are one host
+    // image and one copy
+    enum { RESULT, MAT_ET, DST, POS, ITEMS };
+    const auto l = lay_out({64, (size_t)n * stride * sizeof(uint32_t), (size_t)nq * sizeof(uint32_t), (size_t)nq * sizeof(uint32_t),
+                            (size_t)n_items * sizeof(PathsItem)});
+    // (before blk: a call that leaves early still outlives the copy out of it)
+    std::vector<unsigned char> host(l.total - l.off[DST], 0);
+    l.put(host, DST, DST, P.dst.data(), nq), l.put(host, DST, POS, P.pos.data(), nq), l.put(host, DST, ITEMS, P.items);
     Scratch blk;
-    if (Scratch::make(&blk, total, err) != 0) {
+    if (Scratch::make(&blk, l.total, err) != 0) {
         (void)hipGetLastError();
         return -2;
     }
-    unsigned long long* result = blk.at<unsigned long long>(0);
-    uint32_t* ET = blk.at<uint32_t>(off_et);
-    HIPCHK(hipMemsetAsync(result, 0, off_et, st));
-    HIPCHK(hipMemcpyAsync(blk.at<unsigned char>(off_dst), host.data(), host.size(), hipMemcpyHostToDevice, st));
+    unsigned long long* result = l.at<unsigned long long>(blk, RESULT);
+    uint32_t* ET = l.at<uint32_t>(blk, MAT_ET);
+    HIPCHK(hipMemsetAsync(result, 0, 64, st));
+    HIPCHK(hipMemcpyAsync(l.at<unsigned char>(blk, DST), host.data(), host.size(), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_paths_edges_t, dim3((n + kPathsEdgeCols - 1u) / kPathsEdgeCols, stride / kPathsEdgeWords), dim3(kPathsBlock),
                        0, st, spec.hops, n, stride, ET);
     HIPCHK(hipGetLastError());
     const PathsShape S{n, stride, closure_bit_words(n), out_nodes ? spec.max_len : 0u, n_items, 0, plan.row_bytes};
     const bool via_lds = out_via && plan.via_bytes;
     const uint32_t lds = plan.lds_bytes - (via_lds ? 0u : plan.via_bytes);
-    const PathsItem* items = blk.at<PathsItem>(off_items);
-    const uint32_t *dst = blk.at<uint32_t>(off_dst), *pos = blk.at<uint32_t>(off_pos);
+    const PathsItem* items = l.at<PathsItem>(blk, ITEMS);
+    const uint32_t *dst = l.at<uint32_t>(blk, DST), *pos = l.at<uint32_t>(blk, POS);
     int rc;
 #define PG_WALK(NODES, VIA) \
     launch_walk<NODES, VIA>(blocks_per_cu, S, lds, st, spec.hops, ET, items, dst, pos, out_len, out_nodes, out_via, result, err)

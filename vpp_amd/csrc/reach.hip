@@ -32,8 +32,9 @@
 //
 // No kernel takes or touches a hit counter (k_rules_pairs counts into the caller's arrays).
 //
-// The three drivers are four steps: stage the inputs in one scratch block (lay_out), run each form's
-// prologue (run_prologue), launch its pair kernel (with_words_vec, grid_resident), Scratch::finish.
+// The three drivers are four steps: stage the inputs in one scratch block (Staged), run each form's
+// prologue (run_prologue; run_forms for the matrix and the rules), launch its pair kernel
+// (with_words_vec, grid_resident), Scratch::finish.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -41,7 +42,7 @@
 #include <type_traits>
 #include <vector>
 
-#include "hiputil.hpp"
+#include "audit_launch.hpp"
 #include "ports.hpp"
 #include "reach.hpp"
 #include "rules.hpp"
@@ -229,28 +230,6 @@ __global__ __launch_bounds__(kRulesBlock) void k_rules_pairs(DevTableSet T, Reac
 }
 
 // ---- what the drivers are made of --------------------------------------------------------------------
-// The scratch block of a call is a row of sections, each starting 16-B aligned. Those filled by the
-// host are `copied`: they go in as one copy of the block's first `copied` bytes (a section between
-// them that the kernels fill is copied over as zeros first).
-struct Section {
-    size_t bytes;
-    bool copied;
-};
-template <size_t N>
-struct Layout {
-    size_t off[N], copied, total;
-};
-template <size_t N>
-Layout<N> lay_out(const Section (&s)[N]) {
-    Layout<N> l{};
-    for (size_t i = 0; i < N; i++) {
-        l.off[i] = (l.total + 15u) & ~(size_t)15u;
-        l.total = l.off[i] + s[i].bytes;
-        if (s[i].copied) l.copied = l.total;
-    }
-    return l;
-}
-
 // the prologue of one form: rec (and cls, form A) of the ne end points, g of the n services in list
 template <bool UNI>
 void run_prologue(const DevTableSet& T, const uint32_t* ip, uint32_t ne, const W4* svc, const uint32_t* list, uint32_t n,
@@ -270,101 +249,106 @@ void with_words_vec(bool words, bool vec, const F& f) {
     else f(std::true_type{}, std::false_type{});
 }
 
+// The inputs of a call, staged. The block is [ip of src ++ dst | list | extra | cls | svc | rec | end | g]:
+// the host fills it up to svc and copies that prefix in with one synchronous copy (cls, which the
+// kernels fill, goes over as zeros); rec are form A's records, end form B's ends.
+struct Staged {
+    Scratch blk;
+    uint32_t ns, nd;
+    const uint32_t *ip, *list, *extra;
+    const W4* svc;
+    uint32_t* cls;
+    W4 *rec, *end;
+    W2* g;
+    // list: the ordered services, at most n_svc; extra: one u32 per service, or null; with_end: room for end
+    int make(const ReachSpecDev& s, const std::vector<uint32_t>& list_h, const uint32_t* extra_h, bool with_end, std::string* err) {
+        ns = s.n_src, nd = s.n_dst;
+        const size_t ne = (size_t)ns + nd, nv = s.n_svc;
+        enum { IP, LIST, EXTRA, CLS, SVC, REC, END, G };
+        const auto l = lay_out({4u * ne, 4u * nv, extra_h ? 4u * nv : 0u, 4u * ne, 16u * nv, 16u * ne, with_end ? 16u * ne : 0u,
+                                8u * nv});
+        std::vector<unsigned char> h(l.off[SVC] + 16u * nv, 0);  // the copied prefix
+        l.put(h, IP, IP, s.src_ip, ns), std::copy_n(s.dst_ip, nd, l.in<uint32_t>(h, IP, IP) + ns);
+        l.put(h, IP, LIST, list_h), l.put(h, IP, EXTRA, extra_h, extra_h ? nv : 0u), l.put(h, IP, SVC, s.services, nv);
+        if (Scratch::make(&blk, l.total, err) != 0) return -1;
+        HIPCHK(hipMemcpy(blk.at<unsigned char>(0), h.data(), h.size(), hipMemcpyHostToDevice));
+        ip = l.at<uint32_t>(blk, IP), list = l.at<uint32_t>(blk, LIST), extra = l.at<uint32_t>(blk, EXTRA);
+        cls = l.at<uint32_t>(blk, CLS), svc = l.at<W4>(blk, SVC);
+        rec = l.at<W4>(blk, REC), end = l.at<W4>(blk, END), g = l.at<W2>(blk, G);
+        return 0;
+    }
+};
+
+// The passes of a call whose list is [na form-A services | nb form-B services]: each form's prologue,
+// then launch(uni, wide, the pass without outputs, its words) for the caller's pair kernel
+template <class F>
+void run_forms(const DevTableSet& T, const Staged& in, uint32_t na, uint32_t nb, hipStream_t st, const F& launch) {
+    // one form: its n services lst, its end-point records r and (form A) classes c
+    auto pass = [&](auto uni, auto wide, const uint32_t* lst, uint32_t n, W4* r, uint32_t* c) {
+        run_prologue<decltype(uni)::value>(T, in.ip, in.ns + in.nd, in.svc, lst, n, r, c, in.g, st);
+        launch(uni, wide, ReachPass{{r, r + in.ns, c, c ? c + in.ns : nullptr, in.ns, in.nd}, in.g, lst, n, nullptr, nullptr},
+               (uint64_t)n * in.ns * reach_row_words(in.nd));
+    };
+    if (na && T.node.wide) pass(std::true_type{}, std::true_type{}, in.list, na, in.rec, in.cls);
+    else if (na) pass(std::true_type{}, std::false_type{}, in.list, na, in.rec, in.cls);
+    if (nb) pass(std::false_type{}, std::false_type{}, in.list + na, nb, in.end, nullptr);
+}
+
 }  // namespace
 
 int dev_reach_matrix(const DevTableSet& T, const Tuning& tu, const ReachSpecDev& spec, uint32_t* out_packed,
                      uint32_t* out_words, void* stream, std::string* err) {
-    const uint32_t ns = spec.n_src, nd = spec.n_dst, nv = spec.n_svc, ne = ns + nd;
+    const uint32_t ns = spec.n_src, nd = spec.n_dst, nv = spec.n_svc;
     if (!ns || !nd || !nv) return 0;
     hipStream_t st = (hipStream_t)stream;
-    const bool form_a = reach_form_a(T.node, tu);
-    // the services of each form (the host partitions them): list = [form A ..., form B ...]
     std::vector<uint32_t> list;
-    for (uint32_t v = 0; v < nv; v++)
-        if (form_a && spec.services[v].x <= 2u) list.push_back(v);
-    const uint32_t na = (uint32_t)list.size(), nb = nv - na;
-    for (uint32_t v = 0; v < nv; v++)
-        if (!(form_a && spec.services[v].x <= 2u)) list.push_back(v);
-    enum { IP, LIST, CLS, SVC, REC, END, G };  // rec: form A's records, end: form B's ends
-    const auto l = lay_out({{4u * (size_t)ne, true}, {4u * (size_t)nv, true}, {4u * (size_t)ne, false},
-                            {16u * (size_t)nv, true}, {16u * (size_t)ne, false}, {16u * (size_t)ne, false},
-                            {8u * (size_t)nv, false}});
-    std::vector<unsigned char> h(l.copied, 0);
-    std::copy(spec.src_ip, spec.src_ip + ns, reinterpret_cast<uint32_t*>(h.data() + l.off[IP]));
-    std::copy(spec.dst_ip, spec.dst_ip + nd, reinterpret_cast<uint32_t*>(h.data() + l.off[IP]) + ns);
-    std::copy(list.begin(), list.end(), reinterpret_cast<uint32_t*>(h.data() + l.off[LIST]));
-    std::copy(spec.services, spec.services + nv, reinterpret_cast<W4*>(h.data() + l.off[SVC]));
-    Scratch blk;
-    if (Scratch::make(&blk, l.total, err) != 0) return -1;
-    unsigned char* d = blk.at<unsigned char>(0);
-    HIPCHK(hipMemcpy(d, h.data(), h.size(), hipMemcpyHostToDevice));
-    const uint32_t *ip = blk.at<uint32_t>(l.off[IP]), *dl = blk.at<uint32_t>(l.off[LIST]);
-    uint32_t* cls = blk.at<uint32_t>(l.off[CLS]);
-    const W4* svc = blk.at<W4>(l.off[SVC]);
-    W4 *rec = blk.at<W4>(l.off[REC]), *end = blk.at<W4>(l.off[END]);
-    W2* g = blk.at<W2>(l.off[G]);
-    // one form: its n services lst, its end-point records r and (form A) classes c
-    auto pass = [&](auto uni, auto wide, const uint32_t* lst, uint32_t n, W4* r, uint32_t* c) {
-        run_prologue<decltype(uni)::value>(T, ip, ne, svc, lst, n, r, c, g, st);
-        const ReachPass P{{r, r + ns, c, c ? c + ns : nullptr, ns, nd}, g, lst, n, out_packed, out_words};
-        const uint64_t n_words = (uint64_t)n * ns * reach_row_words(nd);
+    const uint32_t na = reach_form_split(reach_form_a(T.node, tu), spec.services, nv, nullptr, &list);
+    Staged in;
+    if (in.make(spec, list, nullptr, true, err) != 0) return -1;
+    run_forms(T, in, na, nv - na, st, [&](auto uni, auto wide, ReachPass P, uint64_t n_words) {
+        P.out_packed = out_packed, P.out_words = out_words;
         const bool vec = nd % 4u == 0 && ((uintptr_t)out_words & 15u) == 0;
         with_words_vec(out_words != nullptr, vec, [&](auto words, auto v16) {
             auto k = k_reach_pairs<decltype(uni)::value, decltype(wide)::value, decltype(words)::value, decltype(v16)::value>;
             hipLaunchKernelGGL(k, dim3(grid_resident(k, kReachPairBlock, 0, n_words, tu.blocks_per_cu)),
                                dim3(kReachPairBlock), 0, st, T, P, n_words);
         });
-    };
-    if (na && T.node.wide) pass(std::true_type{}, std::true_type{}, dl, na, rec, cls);
-    else if (na) pass(std::true_type{}, std::false_type{}, dl, na, rec, cls);
-    if (nb) pass(std::false_type{}, std::false_type{}, dl + na, nb, end, nullptr);
+    });
     HIPCHK(hipGetLastError());
-    return blk.finish(st, "reach matrix", err);
+    return in.blk.finish(st, "reach matrix", err);
 }
 
 int dev_reach_ports(const DevTableSet& T, const Tuning& tu, const PortsSpecDev& spec, uint32_t* out_codes,
                     uint32_t* out_open, uint32_t* out_words, void* stream, std::string* err) {
-    const uint32_t ns = spec.n_src, nd = spec.n_dst, K = spec.K, ne = ns + nd;
+    const uint32_t ns = spec.n_src, nd = spec.n_dst, K = spec.K;
     if (!ns || !nd || !K) return 0;
     hipStream_t st = (hipStream_t)stream;
     const bool form_a = reach_form_a(T.node, tu);  // (TCP / UDP: every interval takes the same form)
-    enum { IP, LIST, LEN, CLS, SVC, REC, G };
-    const auto l = lay_out({{4u * (size_t)ne, true}, {4u * (size_t)K, true}, {4u * (size_t)K, true},
-                            {4u * (size_t)ne, false}, {16u * (size_t)K, true}, {16u * (size_t)ne, false},
-                            {8u * (size_t)K, false}});
-    std::vector<unsigned char> h(l.copied, 0);
-    std::copy(spec.src_ip, spec.src_ip + ns, reinterpret_cast<uint32_t*>(h.data() + l.off[IP]));
-    std::copy(spec.dst_ip, spec.dst_ip + nd, reinterpret_cast<uint32_t*>(h.data() + l.off[IP]) + ns);
+    // the intervals as services, all in one pass, and their lengths
+    std::vector<uint32_t> list(K), lens(K);
+    std::vector<W4> svc(K);
     for (uint32_t k = 0; k < K; k++) {
-        reinterpret_cast<uint32_t*>(h.data() + l.off[LIST])[k] = k;
-        reinterpret_cast<uint32_t*>(h.data() + l.off[LEN])[k] = ports_len(spec.lo, K, k);
-        reinterpret_cast<W4*>(h.data() + l.off[SVC])[k] = reach_service((int32_t)spec.protocol, spec.src_port, spec.lo[k]);
+        list[k] = k, lens[k] = ports_len(spec.lo, K, k);
+        svc[k] = reach_service((int32_t)spec.protocol, spec.src_port, spec.lo[k]);
     }
-    Scratch blk;
-    if (Scratch::make(&blk, l.total, err) != 0) return -1;
-    unsigned char* d = blk.at<unsigned char>(0);
-    HIPCHK(hipMemcpy(d, h.data(), h.size(), hipMemcpyHostToDevice));
-    const uint32_t *ip = blk.at<uint32_t>(l.off[IP]), *dl = blk.at<uint32_t>(l.off[LIST]);
-    const uint32_t* len = blk.at<uint32_t>(l.off[LEN]);
-    uint32_t* cls = form_a ? blk.at<uint32_t>(l.off[CLS]) : nullptr;
-    const W4* svc = blk.at<W4>(l.off[SVC]);
-    W4* rec = blk.at<W4>(l.off[REC]);
-    W2* g = blk.at<W2>(l.off[G]);
-    const ReachEnds E{rec, rec + ns, cls, form_a ? cls + ns : nullptr, ns, nd};
+    Staged in;
+    if (in.make(ReachSpecDev{spec.src_ip, spec.dst_ip, svc.data(), ns, nd, K}, list, lens.data(), false, err) != 0) return -1;
+    uint32_t* cls = form_a ? in.cls : nullptr;
+    const ReachEnds E{in.rec, in.rec + ns, cls, form_a ? cls + ns : nullptr, ns, nd};
     auto pairs = [&](auto uni, auto wide) {
-        run_prologue<decltype(uni)::value>(T, ip, ne, svc, dl, K, rec, cls, g, st);
+        run_prologue<decltype(uni)::value>(T, in.ip, ns + nd, in.svc, in.list, K, in.rec, cls, in.g, st);
         const bool vec = K % 4u == 0 && ((uintptr_t)out_words & 15u) == 0;
         with_words_vec(out_words != nullptr, vec, [&](auto words, auto v16) {
             auto k = k_ports_pairs<decltype(uni)::value, decltype(wide)::value, decltype(words)::value, decltype(v16)::value>;
             hipLaunchKernelGGL(k, dim3(grid_resident(k, kReachPairBlock, 0, ns * nd, tu.blocks_per_cu)),
-                               dim3(kReachPairBlock), 0, st, T, E, g, len, K, ns * nd, out_codes, out_open, out_words);
+                               dim3(kReachPairBlock), 0, st, T, E, in.g, in.extra, K, ns * nd, out_codes, out_open, out_words);
         });
     };
     if (!form_a) pairs(std::false_type{}, std::false_type{});
     else if (T.node.wide) pairs(std::true_type{}, std::true_type{});
     else pairs(std::true_type{}, std::false_type{});
     HIPCHK(hipGetLastError());
-    return blk.finish(st, "port sweep", err);
+    return in.blk.finish(st, "port sweep", err);
 }
 
 namespace {
@@ -383,8 +367,7 @@ void with_rules_kernel(bool evals, bool cells, bool agg, const F& f) {
 
 int dev_rules_resident(const Tuning& tu, uint32_t lds_bytes) {
     auto k = k_rules_pairs<false, false, true, true, true>;
-    if (lds_bytes > 48u * 1024u)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    (void)allow_dynamic_lds(k, lds_bytes);
     const int g = grid_resident(k, (int)kRulesBlock, lds_bytes, ~(uint64_t)0 >> 1, tu.blocks_per_cu);
     (void)hipGetLastError();  // (a failed occupancy query is answered by grid_resident's fall-back)
     return g;
@@ -393,7 +376,7 @@ int dev_rules_resident(const Tuning& tu, uint32_t lds_bytes) {
 int dev_reach_rules(const DevTableSet& T, const Tuning& tu, const RulesSpecDev& spec, unsigned long long* out_evals,
                     unsigned long long* out_cells, std::vector<uint64_t>* evals_host, void* stream, std::string* err) {
     const ReachSpecDev& rs = spec.reach;
-    const uint32_t ns = rs.n_src, nd = rs.n_dst, nv = rs.n_svc, ne = ns + nd, n_slots = spec.n_slots;
+    const uint32_t ns = rs.n_src, nd = rs.n_dst, nv = rs.n_svc, n_slots = spec.n_slots;
     hipStream_t st = (hipStream_t)stream;
     if (out_evals) HIPCHK(hipMemsetAsync(out_evals, 0, (size_t)n_slots * sizeof(uint64_t), st));
     if (out_cells) HIPCHK(hipMemsetAsync(out_cells, 0, 4u * (size_t)n_slots * sizeof(uint64_t), st));
@@ -407,67 +390,34 @@ int dev_reach_rules(const DevTableSet& T, const Tuning& tu, const RulesSpecDev& 
         HIPCHK(hipStreamSynchronize(st));
         return read_back();
     }
-    const bool form_a = reach_form_a(T.node, tu);
-    // the services of each form that weigh anything: list = [form A ..., form B ...]
+    // (the services that weigh anything)
     std::vector<uint32_t> list;
-    for (uint32_t v = 0; v < nv; v++)
-        if (spec.weight[v] && form_a && rs.services[v].x <= 2u) list.push_back(v);
-    const uint32_t na = (uint32_t)list.size();
-    for (uint32_t v = 0; v < nv; v++)
-        if (spec.weight[v] && !(form_a && rs.services[v].x <= 2u)) list.push_back(v);
-    const uint32_t nb = (uint32_t)list.size() - na;
-    if (!na && !nb) {
+    const uint32_t na = reach_form_split(reach_form_a(T.node, tu), rs.services, nv, spec.weight, &list);
+    if (list.empty()) {
         HIPCHK(hipStreamSynchronize(st));
         return read_back();
     }
-    enum { IP, LIST, WT, CLS, SVC, REC, END, G };  // rec: form A's records, end: form B's ends
-    const auto l = lay_out({{4u * (size_t)ne, true}, {4u * (size_t)nv, true}, {4u * (size_t)nv, true},
-                            {4u * (size_t)ne, false}, {16u * (size_t)nv, true}, {16u * (size_t)ne, false},
-                            {16u * (size_t)ne, false}, {8u * (size_t)nv, false}});
-    std::vector<unsigned char> h(l.copied, 0);
-    std::copy(rs.src_ip, rs.src_ip + ns, reinterpret_cast<uint32_t*>(h.data() + l.off[IP]));
-    std::copy(rs.dst_ip, rs.dst_ip + nd, reinterpret_cast<uint32_t*>(h.data() + l.off[IP]) + ns);
-    std::copy(list.begin(), list.end(), reinterpret_cast<uint32_t*>(h.data() + l.off[LIST]));
-    std::copy(spec.weight, spec.weight + nv, reinterpret_cast<uint32_t*>(h.data() + l.off[WT]));
-    std::copy(rs.services, rs.services + nv, reinterpret_cast<W4*>(h.data() + l.off[SVC]));
-    Scratch blk;
-    if (Scratch::make(&blk, l.total, err) != 0) return -1;
-    unsigned char* d = blk.at<unsigned char>(0);
-    HIPCHK(hipMemcpy(d, h.data(), h.size(), hipMemcpyHostToDevice));
-    const uint32_t *ip = blk.at<uint32_t>(l.off[IP]), *dl = blk.at<uint32_t>(l.off[LIST]);
-    uint32_t* cls = blk.at<uint32_t>(l.off[CLS]);
-    const W4* svc = blk.at<W4>(l.off[SVC]);
-    W4 *rec = blk.at<W4>(l.off[REC]), *end = blk.at<W4>(l.off[END]);
-    W2* g = blk.at<W2>(l.off[G]);
+    Staged in;
+    if (in.make(rs, list, spec.weight, true, err) != 0) return -1;
     const RulesPlan plan = rules_plan(n_slots, spec.n_tail, out_evals != nullptr, out_cells != nullptr, tu.rules_hist_cells,
                                       spec.max_weight);
-    const RulesArgs A{blk.at<uint32_t>(l.off[WT]), out_evals, out_cells, plan.evals, plan.cells, n_slots, plan.flush_words};
+    const RulesArgs A{in.extra, out_evals, out_cells, plan.evals, plan.cells, n_slots, plan.flush_words};
     int rc = 0;
-    // one form: its n services lst, its end-point records r and (form A) classes c
-    auto pass = [&](auto uni, auto wide, const uint32_t* lst, uint32_t n, W4* r, uint32_t* c) {
-        run_prologue<decltype(uni)::value>(T, ip, ne, svc, lst, n, r, c, g, st);
-        const ReachPass P{{r, r + ns, c, c ? c + ns : nullptr, ns, nd}, g, lst, n, nullptr, nullptr};
-        const uint64_t n_words = (uint64_t)n * ns * reach_row_words(nd);
+    run_forms(T, in, na, (uint32_t)list.size() - na, st, [&](auto uni, auto wide, const ReachPass& P, uint64_t n_words) {
         with_rules_kernel<decltype(uni)::value, decltype(wide)::value>(
             out_evals != nullptr, out_cells != nullptr, tu.rules_wave_agg != 0, [&](auto k) {
-                if (plan.lds_bytes > 48u * 1024u &&
-                    hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)plan.lds_bytes) != hipSuccess)
-                    rc = -1;
+                if (allow_dynamic_lds(k, plan.lds_bytes) != hipSuccess) rc = -1;
                 const int grid = grid_resident(k, (int)kRulesBlock, plan.lds_bytes, n_words, tu.blocks_per_cu);
                 (void)hipGetLastError();  // (a failed occupancy query is answered by grid_resident's fall-back)
                 if (rc == 0) hipLaunchKernelGGL(k, dim3(grid), dim3(kRulesBlock), plan.lds_bytes, st, T, P, A, n_words);
             });
-    };
-    if (na && T.node.wide) pass(std::true_type{}, std::true_type{}, dl, na, rec, cls);
-    else if (na) pass(std::true_type{}, std::false_type{}, dl, na, rec, cls);
-    if (nb) pass(std::false_type{}, std::false_type{}, dl + na, nb, end, nullptr);
+    });
     if (rc != 0) {
         if (err) *err = "rule coverage: the LDS window was refused";
         return -1;
     }
     HIPCHK(hipGetLastError());
-    if (blk.finish(st, "rule coverage", err) != 0) return -1;
+    if (in.blk.finish(st, "rule coverage", err) != 0) return -1;
     return read_back();
 }
 

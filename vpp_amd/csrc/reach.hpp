@@ -18,6 +18,9 @@
 // Output: 2 bits per pair, 16 pairs per word (reach_word_*: the unit of work is one output word,
 // 16 consecutive dst of one (service, src), four rounds of Q = 4), and optionally the full words.
 #pragma once
+#include <algorithm>
+#include <vector>
+
 #include "classify.hpp"
 
 namespace pg {
@@ -169,5 +172,14 @@ int dev_reach_matrix(const DevTableSet& T, const Tuning& tu, const ReachSpecDev&
 // whether a call takes form A for the services of protocol <= 2 (the launch's and the host twin's
 // one decision)
 inline bool reach_form_a(const DevNode& nd, const Tuning& tu) { return nd.img && tu.node_path && nd.uniform; }
+// The services of each form: *list = [form A ..., form B ...] -> how many are form A's. With weights
+// (rule coverage), those that weigh nothing are left out.
+inline uint32_t reach_form_split(bool form_a, const W4* svc, uint32_t n, const uint32_t* weight, std::vector<uint32_t>* list) {
+    list->clear();
+    for (uint32_t v = 0; v < n; v++)
+        if (!weight || weight[v]) list->push_back(v);
+    const auto mid = std::stable_partition(list->begin(), list->end(), [&](uint32_t v) { return form_a && svc[v].x <= 2u; });
+    return (uint32_t)(mid - list->begin());
+}
 
 }  // namespace pg

@@ -31,7 +31,7 @@
 #include <algorithm>
 #include <string>
 
-#include "hiputil.hpp"
+#include "audit_launch.hpp"
 #include "zones.hpp"
 
 namespace pg {
@@ -225,8 +225,6 @@ __global__ __launch_bounds__(kZonesBlock) void k_zones_dag(const uint32_t* __res
     }
 }
 
-size_t up16(size_t n) { return (n + 15u) & ~(size_t)15u; }
-
 }  // namespace
 
 int dev_reach_zones(uint32_t blocks_per_cu, const uint32_t* matrix, uint32_t n, const ZonesOutDev& out, ZonesResult* result,
@@ -238,42 +236,41 @@ int dev_reach_zones(uint32_t blocks_per_cu, const uint32_t* matrix, uint32_t n, 
     // (before blk: a call that leaves early still outlives the copy into it)
     uint32_t res[kZonesResultWords] = {};
     Scratch blk;
-    // one block: [B | BT | mark | zsize | label | zid | cnt_b | cnt_bt | result], each padded to 16 B
-    const size_t mat = up16((size_t)n * stride * sizeof(uint32_t)), vec = up16((size_t)n * sizeof(uint32_t));
-    const size_t off_bt = mat, off_mark = 2u * mat, off_zsize = off_mark + vec, off_label = off_zsize + vec;
-    const size_t off_zid = off_label + vec, off_cb = off_zid + vec, off_ct = off_cb + vec, off_res = off_ct + vec;
-    if (Scratch::make(&blk, off_res + up16(kZonesResultWords * sizeof(uint32_t)), err) != 0) {
+    // MARK and ZSIZE are adjacent: one memset clears both (ZSIZE: the sizes beyond kZonesLdsZones zones)
+    enum { MAT_B, MAT_BT, MARK, ZSIZE, LABEL, ZID, CNT_B, CNT_BT, RESULT };
+    const size_t mat = (size_t)n * stride * sizeof(uint32_t), vec = (size_t)n * sizeof(uint32_t);
+    const auto l = lay_out({mat, mat, vec, vec, vec, vec, vec, vec, kZonesResultWords * sizeof(uint32_t)});
+    if (Scratch::make(&blk, l.total, err) != 0) {
         (void)hipGetLastError();
         return -2;
     }
-    uint32_t *B = blk.at<uint32_t>(0), *BT = blk.at<uint32_t>(off_bt), *d_res = blk.at<uint32_t>(off_res);
-    HIPCHK(hipMemsetAsync(blk.at<uint32_t>(off_mark), 0, 2u * vec, st));  // mark and zsize
+    uint32_t *B = l.at<uint32_t>(blk, MAT_B), *BT = l.at<uint32_t>(blk, MAT_BT), *d_res = l.at<uint32_t>(blk, RESULT);
+    uint32_t *d_mark = l.at<uint32_t>(blk, MARK), *d_label = l.at<uint32_t>(blk, LABEL);
+    uint32_t *d_cb = l.at<uint32_t>(blk, CNT_B), *d_ct = l.at<uint32_t>(blk, CNT_BT);
+    HIPCHK(hipMemsetAsync(d_mark, 0, l.off[LABEL] - l.off[MARK], st));
 
     ZonesShape S{n, rw, stride, plan.col_tiles, plan.bits_grid, 0};
-    int grid = grid_resident(k_zones_bits_t, (int)kZonesBlock, 0, (uint64_t)S.items * kZonesBlock, blocks_per_cu);
-    (void)hipGetLastError();  // (a failed occupancy query is answered by grid_resident's fall-back)
-    S.per = (S.items + (uint32_t)grid - 1u) / (uint32_t)grid;
-    hipLaunchKernelGGL(k_zones_bits_t, dim3((S.items + S.per - 1u) / S.per), dim3(kZonesBlock), 0, st, matrix, S, B, BT);
+    const Runs runs = run_grid(k_zones_bits_t, (int)kZonesBlock, 0, S.items, blocks_per_cu);
+    S.per = (uint32_t)runs.per;
+    hipLaunchKernelGGL(k_zones_bits_t, dim3((uint32_t)runs.groups), dim3(kZonesBlock), 0, st, matrix, S, B, BT);
     HIPCHK(hipGetLastError());
 
     auto label = [&](auto kernel) {
         const int g = grid_resident(kernel, (int)kZonesBlock, 0, (uint64_t)plan.label_grid * kZonesBlock, blocks_per_cu);
         (void)hipGetLastError();
-        hipLaunchKernelGGL(kernel, dim3(g), dim3(kZonesBlock), 0, st, B, BT, n, stride, bw, blk.at<uint32_t>(off_label),
-                           blk.at<uint32_t>(off_mark), blk.at<uint32_t>(off_cb), blk.at<uint32_t>(off_ct));
+        hipLaunchKernelGGL(kernel, dim3(g), dim3(kZonesBlock), 0, st, B, BT, n, stride, bw, d_label, d_mark, d_cb, d_ct);
     };
     if (counts) label(k_zones_label<true>);
     else label(k_zones_label<false>);
     HIPCHK(hipGetLastError());
 
-    const ZonesNumberArgs A{blk.at<uint32_t>(off_label), blk.at<uint32_t>(off_mark), B, blk.at<uint32_t>(off_cb),
-                            blk.at<uint32_t>(off_ct), blk.at<uint32_t>(off_zid), blk.at<uint32_t>(off_zsize), n, stride,
+    const ZonesNumberArgs A{d_label, d_mark, B, d_cb, d_ct, l.at<uint32_t>(blk, ZID), l.at<uint32_t>(blk, ZSIZE), n, stride,
                             out.zone, out.rep, out.size, out.reaches, out.reached_by, d_res};
     hipLaunchKernelGGL(k_zones_number, dim3(1), dim3(kZonesNumberBlock), 0, st, A);
     HIPCHK(hipGetLastError());
 
     if (out.dag) {
-        grid = grid_resident(k_zones_dag, (int)kZonesBlock, 0, (uint64_t)plan.dag_grid * kZonesBlock, blocks_per_cu);
+        const int grid = grid_resident(k_zones_dag, (int)kZonesBlock, 0, (uint64_t)plan.dag_grid * kZonesBlock, blocks_per_cu);
         (void)hipGetLastError();
         hipLaunchKernelGGL(k_zones_dag, dim3(grid), dim3(kZonesBlock), 0, st, B, stride, out.rep, d_res, out.dag);
         HIPCHK(hipGetLastError());

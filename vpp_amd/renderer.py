@@ -319,12 +319,8 @@ class Engine:
         services: (protocol, src port, dst port). -> packed u32 [n_svc, n_src, row_words], and the
         full verdict words u32 [n_svc, n_src, n_dst] when ``words``."""
         import numpy as np
-        src = np.ascontiguousarray(src_ips, dtype=np.uint32)
-        dst = np.ascontiguousarray(dst_ips, dtype=np.uint32)
-        svc = (_capi.pg_service * max(1, len(services)))()
-        for i, (proto, sport, dport) in enumerate(services):
-            svc[i].protocol, svc[i].src_port, svc[i].dst_port = int(proto), int(sport), int(dport)
-        spec = _capi.pg_reach_spec(src.ctypes.data, len(src), dst.ctypes.data, len(dst), svc, len(services))
+        from . import device as D
+        spec, (src, dst, _svc) = D.reach_spec(src_ips, dst_ips, services)
         rw = lib.pg_reach_row_words(len(dst))
         packed = np.full((len(services), len(src), rw), 0xFFFFFFFF, np.uint32)
         full = np.full((len(services), len(src), len(dst)), 0xFFFFFFFF, np.uint32) if words else None
