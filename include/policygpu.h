@@ -185,7 +185,8 @@ int pg_ctx_device(const pg_ctx* ctx);
  * -- for tables the cross product cannot take, default 1; 0 = candidate lists; 2 = wherever it
  * fits, for tests), "launch_max_tuples" (a pg_classify batch larger than this takes several
  * kernel launches of at most this many tuples, in order on the stream; a multiple of 64, 0 =
- * the largest a launch's 32-bit stream offsets allow, 2^30 - 64; default 0), "classes_hash_bits"
+ * the largest a launch's 32-bit stream offsets allow, 2^30 - 64; default 0; pg_reach_observed
+ * cuts its flow batch by the same knob), "classes_hash_bits"
  * (pg_reach_classes keeps only this many low bits of every signature, 0..64, 0 = every signature
  * equal; the result does not depend on it, only the rounds of the equality check do -- for tests
  * that reach those rounds at small shapes; default 64), "rules_hist_cells" (pg_reach_rules: cap of
@@ -194,7 +195,13 @@ int pg_ctx_device(const pg_ctx* ctx);
  * does not depend on it -- for tests that reach the global path at small shapes; default 16384 =
  * whatever fits), "rules_wave_agg" (pg_reach_rules: 1/0, the lanes of a wave that hit the first
  * active lane's cell add with one atomic instead of one each; the result does not depend on it;
- * default 1, DESIGN.md has the measurement).
+ * default 1, DESIGN.md has the measurement), "observed_lds_bytes" (pg_reach_observed: cap of the
+ * LDS bytes its two address tables may take in a workgroup, 0..163840; a table that does not fit
+ * is probed in HBM, 0 = never staged; the result does not depend on it -- for tests that reach the
+ * HBM probes at small shapes; default 163840 = whatever fits), "observed_test_first"
+ * (pg_reach_observed: a cell's word is loaded before its atomic OR and the atomic skipped where the
+ * bit shows; 0 = always the atomic, 1 = a plain load, 2 = a load that the CU's L1 does not answer;
+ * the result does not depend on it; default 1, DESIGN.md has the measurement).
  * pg_ctx_set_tuning sets one context's knob; pg_set_tuning sets the process default that
  * contexts created afterwards start from. PG_EINVAL for an unknown key or a value out of range. */
 int pg_ctx_set_tuning(pg_ctx* ctx, const char* key, int value);
@@ -929,6 +936,95 @@ typedef struct pg_reach_zones_plan {
     uint32_t dag_grid;               /* the most workgroups the zone graph can need: one per zone */
 } pg_reach_zones_plan;
 int pg_debug_reach_zones_plan(pg_ctx* ctx, uint32_t n, pg_reach_zones_plan* plan);
+
+/* ---- observed reachability: a flow log as a reach matrix, on the device -----------------------
+ * "Which allowed cells has no flow ever used, and which flows fall on a cell the policy does not
+ * allow?" The other audits say what the policy allows; this one folds what the cluster did -- a
+ * batch of 5-tuples, device-resident like pg_classify's -- into pg_reach_matrix's layout over the
+ * caller's end-point lists and services, so that both answers are existing calls on the device:
+ * pg_reach_diff(before = allowed, after = observed) with PG_DIFF_CLOSED lists the allowed cells no
+ * flow used, with PG_DIFF_OPENED the cells seen but not allowed; pg_reach_groups over the observed
+ * matrix is the per-namespace view.
+ *   End points: flow t has the src index set S = { i : src_ip[i] == flows.src_ip[t] } and the dst
+ *   index set D likewise. Every duplicate in a list counts.
+ *   Services: protocol codes above 3 are read as 3 on both sides, as pg_classify does. Service v
+ *   matches flow t when the protocols are equal and, for TCP and UDP only, dst_port is equal; with
+ *   PG_OBSERVED_MATCH_SRC_PORT src_port must be equal as well, for TCP and UDP. flows->src_port is
+ *   read only with that flag and may otherwise be null. V = the matching services; several services
+ *   may share a key.
+ *   Status of a flow, the first that applies: S empty PG_OBS_NO_SRC, D empty PG_OBS_NO_DST, V empty
+ *   PG_OBS_NO_SVC, otherwise PG_OBS_MATCHED. A matched flow marks every cell of V x S x D.
+ *   out_packed     device, required: pg_reach_matrix's out_packed layout exactly, n_svc * n_src rows of
+ *                  pg_reach_row_words(n_dst) words. Marked cells hold PG_CONN_ALLOW, all others
+ *                  PG_CONN_DENY_SYN, padding bits zero. Without PG_OBSERVED_ACCUMULATE the call clears
+ *                  it on the stream first; with it the call ORs into what is there -- the caller
+ *                  vouches that an earlier call with the same lists wrote it. A valid before / after
+ *                  of pg_reach_diff and input of pg_reach_groups, pg_reach_classes, pg_reach_closure
+ *   out_flow       device, optional, n bytes: the status of every flow at its own position
+ *   out_svc_flows  device, optional, n_svc u64: the matched flows with v in V; every entry is written.
+ *                  Integer sums: exact, and the same on every run
+ *   result         host, required
+ * Like pg_reach_diff the call reads no table and triggers no compile, and it never touches the hit
+ * counters or their snapshots; ctx only names the device and its knobs ("blocks_per_cu",
+ * "launch_max_tuples", "observed_lds_bytes", "observed_test_first" -- the result depends on none).
+ * The flow arrays need their element's own alignment and nothing more (arrays that all start at
+ * 16-B boundaries are read with 16-B loads). Any byte in proto and any port value is valid input; on
+ * any input the call ends and stays inside its arrays. It copies the tables built from the lists in,
+ * enqueues in order on hip_stream and synchronises it before it returns.
+ * n == 0: PG_OK, the outputs cleared as above (out_packed kept with ACCUMULATE), n_cells counted, the
+ * other result fields zero; flows may then be null. An empty side: PG_OK, *result zeroed, every flow
+ * PG_OBS_NO_SRC or PG_OBS_NO_DST in out_flow, out_svc_flows cleared; out_packed has no words.
+ * PG_EINVAL (pg_last_error says which): a null spec, result or out_packed, null flows with n > 0; a
+ * null required flow field; a null list of a side that is not empty, or null services; n_svc 0 or
+ * above 4096; a side above 2^20; n_svc * n_src * row_words >= 2^32; unknown flag bits. PG_ENOMEM: the
+ * scratch allocation (the tables: 12 B per cell of at least twice a list's length, 4 B per end
+ * point) failed. */
+enum { PG_OBS_MATCHED = 0, PG_OBS_NO_SRC = 1, PG_OBS_NO_DST = 2, PG_OBS_NO_SVC = 3 };
+#define PG_OBSERVED_ACCUMULATE     1u  /* out_packed holds an earlier result of the same shape: OR into it, do not clear */
+#define PG_OBSERVED_MATCH_SRC_PORT 2u  /* a TCP/UDP flow matches a service only if src_port is equal too */
+typedef struct pg_reach_observed_spec {
+    const uint32_t* src_ip;   /* host arrays, host-order IPv4, as in pg_reach_spec; duplicates allowed */
+    size_t n_src;
+    const uint32_t* dst_ip;
+    size_t n_dst;
+    const pg_service* services; /* host, 1 .. 4096 */
+    size_t n_svc;
+    uint32_t flags;           /* PG_OBSERVED_* */
+} pg_reach_observed_spec;
+typedef struct pg_reach_observed_result {   /* host */
+    uint64_t n_matched, n_no_src, n_no_dst, n_no_svc;   /* sum == n */
+    uint64_t n_cells;                                   /* ALLOW cells of out_packed after the call */
+} pg_reach_observed_result;
+int pg_reach_observed(pg_ctx* ctx, const pg_reach_observed_spec* spec, const pg_tuple_soa* flows, uint64_t n,
+                      uint32_t* out_packed, uint8_t* out_flow, uint64_t* out_svc_flows, pg_reach_observed_result* result,
+                      void* hip_stream);
+/* TESTS ONLY -- never on the audit path: pg_reach_observed's tables and per-flow code (observed.hpp,
+ * the functions the kernel calls) on the host, flow by flow; the flow arrays and every output are
+ * host arrays. Does not touch the device. */
+int pg_debug_reach_observed_host(pg_ctx* ctx, const pg_reach_observed_spec* spec, const pg_tuple_soa* flows, uint64_t n,
+                                 uint32_t* out_packed, uint8_t* out_flow, uint64_t* out_svc_flows,
+                                 pg_reach_observed_result* result);
+/* TESTS ONLY: how a pg_reach_observed over lists of these lengths is laid out under the context's
+ * knobs ("observed_lds_bytes", "blocks_per_cu"), from the one function the launch itself uses
+ * (observed.hpp observed_plan). A launch takes tiles of block * vec_flows flows (block on the scalar
+ * path), one run of tiles per workgroup. Launches nothing; without a device the grid is that of 256
+ * CUs with one workgroup each, the rest is the same. */
+typedef struct pg_reach_observed_plan {
+    uint32_t src_cap, dst_cap;         /* cells of the address tables: powers of two, at least twice the list */
+    uint32_t src_in_lds, dst_in_lds;   /* 1: staged in LDS by every workgroup, 0: probed in HBM */
+    uint32_t svc_bytes, lds_bytes;     /* LDS of the service table and the counters; all dynamic LDS */
+    uint32_t block, vec_flows;         /* lanes of a workgroup; flows of a lane per step on the vector path */
+    uint32_t grid;                     /* the most workgroups of a launch: the resident ones */
+} pg_reach_observed_plan;
+int pg_debug_reach_observed_plan(pg_ctx* ctx, size_t n_src, size_t n_dst, size_t n_svc, pg_reach_observed_plan* plan);
+/* TESTS ONLY: where the address table built over list[0 .. n_list) finds each of n addresses, read
+ * off the host table by a plain loop, as pg_debug_endpoint_probe does for the end-point table:
+ * out_slot[i] = the cell the probe of ips[i] starts at, out_steps[i] = the cells it reads until it
+ * hits the address or an empty cell (1 = the first cell decides), *out_cap = the table's cells (a
+ * probe wraps from cell cap - 1 to cell 0). Any output may be null. Tests use it to show that their
+ * inputs reach a collision chain or a wrap -- never for an expected value. */
+int pg_debug_reach_observed_probe(pg_ctx* ctx, const uint32_t* list, size_t n_list, const uint32_t* ips, uint64_t n,
+                                  uint32_t* out_steps, uint32_t* out_slot, uint32_t* out_cap);
 
 /* ---- rule coverage: per-rule histograms of a reach product, on the device --------------------
  * "Which rules do any work over my inventory, which are dead or shadowed, and which rule denies the

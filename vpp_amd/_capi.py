@@ -154,6 +154,26 @@ class pg_reach_zones_plan(C.Structure):
                 ("label_grid", C.c_uint32), ("dag_grid", C.c_uint32)]
 
 
+OBS_MATCHED, OBS_NO_SRC, OBS_NO_DST, OBS_NO_SVC = 0, 1, 2, 3
+OBSERVED_ACCUMULATE, OBSERVED_MATCH_SRC_PORT = 1, 2
+
+
+class pg_reach_observed_spec(C.Structure):
+    _fields_ = [("src_ip", C.c_void_p), ("n_src", C.c_size_t), ("dst_ip", C.c_void_p), ("n_dst", C.c_size_t),
+                ("services", C.POINTER(pg_service)), ("n_svc", C.c_size_t), ("flags", C.c_uint32)]
+
+
+class pg_reach_observed_result(C.Structure):
+    _fields_ = [("n_matched", C.c_uint64), ("n_no_src", C.c_uint64), ("n_no_dst", C.c_uint64),
+                ("n_no_svc", C.c_uint64), ("n_cells", C.c_uint64)]
+
+
+class pg_reach_observed_plan(C.Structure):
+    _fields_ = [("src_cap", C.c_uint32), ("dst_cap", C.c_uint32), ("src_in_lds", C.c_uint32),
+                ("dst_in_lds", C.c_uint32), ("svc_bytes", C.c_uint32), ("lds_bytes", C.c_uint32),
+                ("block", C.c_uint32), ("vec_flows", C.c_uint32), ("grid", C.c_uint32)]
+
+
 class pg_reach_rules_spec(C.Structure):
     _fields_ = [("src_ip", C.c_void_p), ("n_src", C.c_size_t), ("dst_ip", C.c_void_p), ("n_dst", C.c_size_t),
                 ("services", C.POINTER(pg_service)), ("n_svc", C.c_size_t), ("svc_weight", C.c_void_p),
@@ -348,6 +368,12 @@ _SIGS = {
     "pg_debug_reach_zones_host": (C.c_int, [_P, C.POINTER(pg_reach_zones_spec), _P, _P, _P, _P, _P, _P,
                                             C.POINTER(pg_reach_zones_result)]),
     "pg_debug_reach_zones_plan": (C.c_int, [_P, C.c_uint32, C.POINTER(pg_reach_zones_plan)]),
+    "pg_reach_observed": (C.c_int, [_P, C.POINTER(pg_reach_observed_spec), C.POINTER(pg_tuple_soa), C.c_uint64, _P, _P, _P,
+                                    C.POINTER(pg_reach_observed_result), _P]),
+    "pg_debug_reach_observed_host": (C.c_int, [_P, C.POINTER(pg_reach_observed_spec), C.POINTER(pg_tuple_soa), C.c_uint64,
+                                               _P, _P, _P, C.POINTER(pg_reach_observed_result)]),
+    "pg_debug_reach_observed_plan": (C.c_int, [_P, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(pg_reach_observed_plan)]),
+    "pg_debug_reach_observed_probe": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_uint64, _P, _P, C.POINTER(C.c_uint32)]),
     "pg_reach_rules": (C.c_int, [_P, C.POINTER(pg_reach_rules_spec), _P, _P, C.POINTER(pg_reach_rules_result), _P]),
     "pg_debug_reach_rules_host": (C.c_int, [_P, C.POINTER(pg_reach_rules_spec), _P, _P,
                                             C.POINTER(pg_reach_rules_result), C.c_int]),

@@ -1,6 +1,6 @@
 // extern "C" boundary of the reachability audits (include/policygpu.h): the matrix, the rule
-// coverage, the port sweep, the diff, the closure, the groups, the paths, the classes and the zones,
-// each with the host twin the tests compare its kernels to.
+// coverage, the port sweep, the diff, the closure, the groups, the paths, the classes, the zones and
+// the observed matrix, each with the host twin the tests compare its kernels to.
 #include <algorithm>
 #include <numeric>
 
@@ -9,6 +9,7 @@
 #include "closure.hpp"
 #include "diff.hpp"
 #include "groups.hpp"
+#include "observed.hpp"
 #include "paths.hpp"
 #include "ports.hpp"
 #include "rules.hpp"
@@ -1210,6 +1211,152 @@ int pg_debug_reach_zones_plan(pg_ctx* ctx, uint32_t n, pg_reach_zones_plan* plan
     const ZonesPlan p = zones_plan(n);
     *plan = pg_reach_zones_plan{p.tile_rows, p.tile_cols, p.row_tiles, p.col_tiles, p.bits_grid, p.label_rows, p.label_grid, p.dag_grid};
     return PG_OK;
+}
+
+}  // extern "C"
+
+// ---- observed reachability (observed.hpp) --------------------------------------------------------
+namespace {
+static_assert(sizeof(pg_reach_observed_result) == sizeof(ObservedResult), "pg_reach_observed_result is observed.hpp's ObservedResult");
+static_assert(sizeof(pg_reach_observed_plan) == sizeof(ObservedPlan), "pg_reach_observed_plan is observed.hpp's ObservedPlan");
+static_assert(PG_OBS_MATCHED == kObsMatched && PG_OBS_NO_SRC == kObsNoSrc && PG_OBS_NO_DST == kObsNoDst && PG_OBS_NO_SVC == kObsNoSvc &&
+                  PG_OBSERVED_ACCUMULATE == kObsAccumulate && PG_OBSERVED_MATCH_SRC_PORT == kObsMatchSrcPort,
+              "observed.hpp's constants are the header's");
+
+int observed_shape(pg_ctx* ctx, size_t n_src, size_t n_dst, size_t n_svc) {
+    if (!n_svc || n_svc > kObsMaxSvc) return fail(ctx, PG_EINVAL, "n_svc is 0 or above 4096");
+    if (n_src > kObsMaxSide || n_dst > kObsMaxSide) return fail(ctx, PG_EINVAL, "a side longer than 2^20");
+    return PG_OK;
+}
+
+// argument checks shared by pg_reach_observed and its host twin
+int observed_args(pg_ctx* ctx, const pg_reach_observed_spec* spec, const pg_tuple_soa* flows, uint64_t n,
+                  const uint32_t* out_packed, const pg_reach_observed_result* result) {
+    if (!ctx) return PG_EINVAL;
+    if (!spec || !result || !out_packed) return fail(ctx, PG_EINVAL, "null spec, result or out_packed");
+    if (spec->flags & ~kObsFlagsAll) return fail(ctx, PG_EINVAL, "unknown flag bits");
+    if (int rc = observed_shape(ctx, spec->n_src, spec->n_dst, spec->n_svc)) return rc;
+    // (n_svc * n_src <= 2^32 and row_words <= 2^16: the product fits 64 bits)
+    if ((uint64_t)spec->n_svc * spec->n_src * reach_row_words(spec->n_dst) >> 32)
+        return fail(ctx, PG_EINVAL, "n_svc * n_src * row_words reaches 2^32");
+    if ((spec->n_src && !spec->src_ip) || (spec->n_dst && !spec->dst_ip) || !spec->services)
+        return fail(ctx, PG_EINVAL, "null src_ip, dst_ip or services");
+    if (n && !flows) return fail(ctx, PG_EINVAL, "null flows");
+    if (n && (!flows->src_ip || !flows->dst_ip || !flows->dst_port || !flows->proto))
+        return fail(ctx, PG_EINVAL, "null flows src_ip, dst_ip, dst_port or proto");
+    if (n && (spec->flags & kObsMatchSrcPort) && !flows->src_port)
+        return fail(ctx, PG_EINVAL, "PG_OBSERVED_MATCH_SRC_PORT needs flows src_port");
+    return PG_OK;
+}
+
+struct ObservedTables {
+    ObservedSide src, dst;
+    ObservedSvc svc;
+    explicit ObservedTables(const pg_reach_observed_spec* spec)
+        : src(observed_side(spec->src_ip, (uint32_t)spec->n_src)),
+          dst(observed_side(spec->dst_ip, (uint32_t)spec->n_dst)),
+          svc(observed_svc((uint32_t)spec->n_svc, (spec->flags & kObsMatchSrcPort) != 0,
+                           [&](uint32_t v, uint32_t* p, uint32_t* sp, uint32_t* dp) {
+                               const pg_service& s = spec->services[v];
+                               *p = (uint32_t)s.protocol, *sp = s.src_port, *dp = s.dst_port;
+                           })) {}
+};
+
+// an empty side: *result is zeroed whatever the flows were
+void observed_finish(const pg_reach_observed_spec* spec, const ObservedResult& r, pg_reach_observed_result* result) {
+    if (!spec->n_src || !spec->n_dst) *result = pg_reach_observed_result{0, 0, 0, 0, 0};
+    else *result = pg_reach_observed_result{r.n_matched, r.n_no_src, r.n_no_dst, r.n_no_svc, r.n_cells};
+}
+}  // namespace
+
+extern "C" {
+
+int pg_reach_observed(pg_ctx* ctx, const pg_reach_observed_spec* spec, const pg_tuple_soa* flows, uint64_t n,
+                      uint32_t* out_packed, uint8_t* out_flow, uint64_t* out_svc_flows, pg_reach_observed_result* result,
+                      void* stream) {
+    GUARD_BEGIN
+    if (int rc = observed_args(ctx, spec, flows, n, out_packed, result)) return rc;
+    DEVICE_GUARD(ctx);
+    const ObservedTables T(spec);
+    const Tuning& tu = ctx->eng.tune;
+    const ObservedKnobs knobs{tu.blocks_per_cu, tu.observed_lds_bytes, tu.observed_test_first, tu.launch_max_tuples};
+    ObservedSpecDev sd{&T.src, &T.dst, &T.svc, (uint32_t)spec->n_src, (uint32_t)spec->n_dst, (uint32_t)spec->n_svc, spec->flags,
+                       nullptr, nullptr, nullptr, nullptr, nullptr, n};
+    if (n) sd.f_src = flows->src_ip, sd.f_dst = flows->dst_ip, sd.f_sport = flows->src_port, sd.f_dport = flows->dst_port, sd.f_proto = flows->proto;
+    std::string err;
+    ObservedResult r{0, 0, 0, 0, 0};
+    const int rc = dev_reach_observed(knobs, sd, out_packed, out_flow, out_svc_flows, &r, stream, &err);
+    if (rc != 0) return fail(ctx, rc == -2 ? PG_ENOMEM : PG_EIO, err);
+    observed_finish(spec, r, result);
+    return PG_OK;
+    GUARD_END(ctx)
+}
+
+int pg_debug_reach_observed_host(pg_ctx* ctx, const pg_reach_observed_spec* spec, const pg_tuple_soa* flows, uint64_t n,
+                                 uint32_t* out_packed, uint8_t* out_flow, uint64_t* out_svc_flows,
+                                 pg_reach_observed_result* result) {
+    GUARD_BEGIN
+    if (int rc = observed_args(ctx, spec, flows, n, out_packed, result)) return rc;
+    const ObservedTables T(spec);
+    const uint32_t nv = (uint32_t)spec->n_svc, rw = (uint32_t)reach_row_words(spec->n_dst);
+    const uint64_t n_words = (uint64_t)nv * spec->n_src * rw;
+    const bool sport = (spec->flags & kObsMatchSrcPort) != 0;
+    if (!(spec->flags & kObsAccumulate)) std::fill(out_packed, out_packed + n_words, 0u);
+    const ObsView<const uint32_t*> V{T.src.tab.data(), T.dst.tab.data(), T.src.idx.data(), T.dst.idx.data(), T.svc.keys.data(),
+                                     T.svc.start.data(), T.svc.idx.data(), T.src.cap - 1u, T.dst.cap - 1u, T.svc.nk,
+                                     (uint32_t)spec->n_src, rw, sport};
+    // every flow in order, as a lane of k_observed runs it; the counts per key, then per service
+    uint64_t status[4] = {0, 0, 0, 0};
+    std::vector<uint64_t> kcnt(T.svc.nk, 0);
+    for (uint64_t t = 0; t < n; t++) {
+        uint32_t k = 0;
+        const uint32_t st = obs_flow(V, flows->src_ip[t], flows->dst_ip[t], sport ? flows->src_port[t] : 0u, flows->dst_port[t],
+                                     flows->proto[t], &k, [&](uint32_t w, uint32_t bit) { out_packed[w] |= bit; });
+        if (st == kObsMatched) kcnt[k]++;
+        status[st]++;
+        if (out_flow) out_flow[t] = (uint8_t)st;
+    }
+    if (out_svc_flows) {
+        std::fill(out_svc_flows, out_svc_flows + nv, (uint64_t)0);
+        for (uint32_t k = 0; k < T.svc.nk; k++)
+            for (uint32_t q = T.svc.start[k]; q < T.svc.start[k + 1]; q++) out_svc_flows[T.svc.idx[q]] = kcnt[k];
+    }
+    uint64_t cells = 0;
+    for (uint64_t w = 0; w < n_words; w++) cells += obs_allow_cells(out_packed[w]);
+    observed_finish(spec, ObservedResult{status[kObsMatched], status[kObsNoSrc], status[kObsNoDst], status[kObsNoSvc], cells}, result);
+    return PG_OK;
+    GUARD_END(ctx)
+}
+
+int pg_debug_reach_observed_plan(pg_ctx* ctx, size_t n_src, size_t n_dst, size_t n_svc, pg_reach_observed_plan* plan) {
+    if (!ctx || !plan) return PG_EINVAL;
+    GUARD_BEGIN
+    if (int rc = observed_shape(ctx, n_src, n_dst, n_svc)) return rc;
+    // (no DEVICE_GUARD: without a device the queries fail and the grid is their fall-back, the rest is host arithmetic)
+    const pg::DeviceGuard guard(ctx);
+    const ObservedPlan p = dev_observed_plan((uint32_t)n_src, (uint32_t)n_dst, (uint32_t)n_svc, ctx->eng.tune.observed_lds_bytes,
+                                             ctx->eng.tune.blocks_per_cu);
+    *plan = pg_reach_observed_plan{p.src_cap, p.dst_cap, p.src_in_lds, p.dst_in_lds, p.svc_bytes, p.lds_bytes, p.block, p.vec_flows, p.grid};
+    return PG_OK;
+    GUARD_END(ctx)
+}
+
+int pg_debug_reach_observed_probe(pg_ctx* ctx, const uint32_t* list, size_t n_list, const uint32_t* ips, uint64_t n,
+                                  uint32_t* out_steps, uint32_t* out_slot, uint32_t* out_cap) {
+    if (!ctx) return PG_EINVAL;
+    GUARD_BEGIN
+    if (n_list > kObsMaxSide) return fail(ctx, PG_EINVAL, "a list longer than 2^20");
+    if ((n_list && !list) || (n && !ips)) return fail(ctx, PG_EINVAL, "null list or ips");
+    const ObservedSide s = observed_side(list, (uint32_t)n_list);
+    if (out_cap) *out_cap = s.cap;
+    for (uint64_t i = 0; i < n; i++) {
+        uint32_t first = 0, count = 0, steps = 0;
+        (void)obs_find(s.tab.data(), s.cap - 1u, ips[i], &first, &count, &steps);
+        if (out_steps) out_steps[i] = steps;
+        if (out_slot) out_slot[i] = obs_hash(ips[i], s.cap - 1u);
+    }
+    return PG_OK;
+    GUARD_END(ctx)
 }
 
 }  // extern "C"

@@ -583,6 +583,59 @@ def reach_zones(engine, closure, n, reps=False, sizes=False, counts=False, dag=F
     return zone, cut(rep), cut(size), cut(out), cut(by), graph, zones_result(res)
 
 
+# ---- observed reachability (include/policygpu.h pg_reach_observed) ---------------------------
+def observed_spec(src_ips, dst_ips, services, flags=0):
+    """pg_reach_observed_spec over host arrays (reach_spec's, and the PG_OBSERVED_* flags) -> (spec,
+    the arrays it points into: keep them alive for the call)"""
+    src = np.ascontiguousarray(src_ips, dtype=np.uint32)
+    dst = np.ascontiguousarray(dst_ips, dtype=np.uint32)
+    svc = (_capi.pg_service * max(1, len(services)))()
+    for i, (proto, sport, dport) in enumerate(services):
+        svc[i].protocol, svc[i].src_port, svc[i].dst_port = int(proto), int(sport), int(dport)
+    spec = _capi.pg_reach_observed_spec(src.ctypes.data if len(src) else None, len(src), dst.ctypes.data if len(dst) else None,
+                                        len(dst), svc, len(services), int(flags))
+    return spec, (src, dst, svc)
+
+
+def observed_result(res):
+    return {"n_matched": res.n_matched, "n_no_src": res.n_no_src, "n_no_dst": res.n_no_dst, "n_no_svc": res.n_no_svc,
+            "n_cells": res.n_cells}
+
+
+def reach_observed(engine, src_ips, dst_ips, services, batch, n=None, match_src_port=False, into=None, flow=False,
+                   svc_flows=False, stream=None):
+    """A flow log folded into reach_matrix's layout, on the GPU (pg_reach_observed): cell (v, i, j) is ALLOW
+    where some flow of the TupleBatch ``batch`` (its first ``n``) went from src_ips[i] to dst_ips[j] on
+    services[v] (protocol, src port, dst port; the src port counts only with ``match_src_port``), DENY_SYN
+    elsewhere. -> (packed, flow, svc_flows, result): the int32 tensor [n_svc, n_src, row_words] -- ``into``,
+    an earlier result of the same lists, is ORed into and returned -- with ``flow`` the PG_OBS_* status of
+    every flow as a uint8 tensor [n], with ``svc_flows`` the matched flows of every service as an int64
+    tensor [n_svc], and {n_matched, n_no_src, n_no_dst, n_no_svc, n_cells}. Whatever was not asked for is
+    None. The result compares with reach_matrix's by reach_diff. The call never touches the hit counters."""
+    flags = (_capi.OBSERVED_MATCH_SRC_PORT if match_src_port else 0) | (_capi.OBSERVED_ACCUMULATE if into is not None else 0)
+    spec, keep = observed_spec(src_ips, dst_ips, services, flags)
+    n = batch.n if n is None else int(n)
+    shape = (len(services), spec.n_src, reach_row_words(spec.n_dst))
+    if into is not None:
+        if into.dtype != torch.int32 or not into.is_contiguous() or tuple(into.shape) != shape:
+            raise ValueError("a contiguous int32 tensor [n_svc, n_src, row_words(n_dst)] expected")
+        packed = into
+    else:
+        packed = torch.empty(shape, dtype=torch.int32, device="cuda")
+    out_flow = torch.empty(n, dtype=torch.uint8, device="cuda") if flow else None
+    counts = torch.empty(len(services), dtype=torch.int64, device="cuda") if svc_flows else None
+    res = _capi.pg_reach_observed_result()
+    soa = batch.soa()
+    if not match_src_port:
+        soa.src_port = None
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+    # (an empty matrix has no address to hand over, but the call wants one: nothing is written through it)
+    engine._ck(lib.pg_reach_observed(engine.h, C.byref(spec), C.byref(soa), n, ptr(packed) or 16, ptr(out_flow), ptr(counts),
+                                     C.byref(res), _stream_ptr(stream)))
+    del keep
+    return packed, out_flow, counts, observed_result(res)
+
+
 # ---- rule coverage (include/policygpu.h pg_reach_rules) ---------------------------------------
 def rules_spec(src_ips, dst_ips, services, weights, n_slots):
     """pg_reach_rules_spec over host arrays (reach_spec's, and the weights as u32 or None) -> (spec,

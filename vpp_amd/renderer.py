@@ -797,6 +797,59 @@ class Engine:
         self._ck(lib.pg_debug_reach_zones_plan(self.h, int(n), C.byref(p)))
         return {name: getattr(p, name) for name, _ in p._fields_}
 
+    def reach_observed(self, src_ips, dst_ips, services, batch, **kw):
+        """A flow log as a reach matrix on the GPU: device.reach_observed on this engine (which only names
+        the device: the call reads no table)."""
+        from . import device as D
+        return D.reach_observed(self, src_ips, dst_ips, services, batch, **kw)
+
+    def debug_reach_observed_host(self, src_ips, dst_ips, services, flows, flags=0, into=None, flow=True, svc_flows=True):
+        """TESTS ONLY: pg_reach_observed's tables and per-flow code run on the host
+        (pg_debug_reach_observed_host). flows: numpy arrays (src, dst, src port or None, dst port, proto);
+        flags: PG_OBSERVED_*; into: packed words that ACCUMULATE ORs into. -> (packed u32 [n_svc, n_src,
+        row_words], flow statuses u8 [n], flows per service u64 [n_svc], {n_matched, .., n_cells}), None
+        for what was not asked for."""
+        import numpy as np
+        from . import device as D
+        spec, keep = D.observed_spec(src_ips, dst_ips, services, flags)
+        src, dst, sport, dport, proto = flows
+        arrs = [np.ascontiguousarray(src, np.uint32), np.ascontiguousarray(dst, np.uint32),
+                None if sport is None else np.ascontiguousarray(sport, np.uint16), np.ascontiguousarray(dport, np.uint16),
+                np.ascontiguousarray(proto, np.uint8)]
+        n = len(arrs[0])
+        soa = _capi.pg_tuple_soa(*[None if a is None else a.ctypes.data for a in arrs])
+        shape = (len(services), spec.n_src, lib.pg_reach_row_words(spec.n_dst))
+        packed = np.full(shape, 0xFFFFFFFF, np.uint32) if into is None else np.ascontiguousarray(into, np.uint32).reshape(shape).copy()
+        out_flow = np.full(n, 0xFF, np.uint8) if flow else None
+        counts = np.full(len(services), 0xFFFFFFFFFFFFFFFF, np.uint64) if svc_flows else None
+        res = _capi.pg_reach_observed_result()
+        p = lambda x: x.ctypes.data_as(C.c_void_p) if x is not None else None
+        self._ck(lib.pg_debug_reach_observed_host(self.h, C.byref(spec), C.byref(soa), n,
+                                                  p(packed) if packed.size else C.c_void_p(16), p(out_flow), p(counts),
+                                                  C.byref(res)))
+        del keep
+        return packed, out_flow, counts, D.observed_result(res)
+
+    def debug_reach_observed_plan(self, n_src, n_dst, n_svc):
+        """TESTS ONLY: how pg_reach_observed over lists of these lengths is laid out under this context's
+        knobs (pg_debug_reach_observed_plan) -> {src_cap, dst_cap, src_in_lds, dst_in_lds, svc_bytes,
+        lds_bytes, block, vec_flows, grid}"""
+        p = _capi.pg_reach_observed_plan()
+        self._ck(lib.pg_debug_reach_observed_plan(self.h, int(n_src), int(n_dst), int(n_svc), C.byref(p)))
+        return {name: getattr(p, name) for name, _ in p._fields_}
+
+    def debug_reach_observed_probe(self, ip_list, ips):
+        """TESTS ONLY: where the address table pg_reach_observed builds over ``ip_list`` finds each address
+        (pg_debug_reach_observed_probe) -> (probe steps u32 [n], start slot u32 [n], the table's capacity)"""
+        import numpy as np
+        ip_list = np.ascontiguousarray(ip_list, dtype=np.uint32)
+        ips = np.ascontiguousarray(ips, dtype=np.uint32)
+        steps, slot, cap = np.zeros(len(ips), np.uint32), np.zeros(len(ips), np.uint32), C.c_uint32()
+        p = lambda x: x.ctypes.data_as(C.c_void_p) if len(x) else None
+        self._ck(lib.pg_debug_reach_observed_probe(self.h, p(ip_list), len(ip_list), p(ips), len(ips), p(steps), p(slot),
+                                                   C.byref(cap)))
+        return steps, slot, cap.value
+
     def _zones(self, ips, services, host, **kw):
         """one _closure (max_hops 0) and one pg_reach_zones over it -> (closure words, reach_zones's
         tuple), device tensors or with ``host`` numpy arrays"""
