@@ -937,6 +937,87 @@ typedef struct pg_reach_zones_plan {
 } pg_reach_zones_plan;
 int pg_debug_reach_zones_plan(pg_ctx* ctx, uint32_t n, pg_reach_zones_plan* plan);
 
+/* ---- reachability dominators: the end points every attack path must cross, on the device -----
+ * "The attacker holds these pods; which single pod, if quarantined, cuts them off from the most
+ * targets, and which pods stand between them and v on every route?" The input has pg_reach_closure's
+ * form: a pg_reach_matrix out_packed taken with one end-point list on both sides (n_svc slices of n
+ * rows of pg_reach_row_words(n) words), which stays on the device, an optional svc_select, and a host
+ * list of entry end points E, the foothold.
+ *   Edge i -> j: some selected slice holds PG_CONN_ALLOW in cell (i, j) -- pg_reach_closure's rule. Cell
+ *   (i, i) is a cell like any other.
+ *   v is reached when v is in E, or some walk of one or more edges leads from a member of E to v.
+ *   k dominates a reached v when every walk from any member of E to v contains k; the walk of no
+ *   edges counts when v is in E. So v dominates itself, an entry is dominated by itself only, a
+ *   single entry dominates every reached end point, and an unreached end point has no dominators.
+ *   Dom(v) is a chain under dominance: |Dom(.)| strictly increases along it.
+ *   idom(v): the k in Dom(v) \ {v} with |Dom(k)| == |Dom(v)| - 1; exactly one when Dom(v) \ {v} is
+ *   not empty, none otherwise.
+ *   cut[k]: the number of v != k with k in Dom(v) -- the end points the attacker loses when k alone is
+ *   quarantined.
+ *   out_dom   device, optional, n rows of pg_reach_row_words(n) words in the audits' layout: cell (v, k)
+ *             holds PG_CONN_ALLOW iff k is in Dom(v), else PG_CONN_DENY_SYN; the padding bits of a row's
+ *             last word are zero and every word is written. A valid before / after of pg_reach_diff
+ *             (which lists the choke points a policy change created or removed) and a valid input of
+ *             pg_reach_groups
+ *   out_idom  device, optional, n uint16_t, each written: idom(v), or 0xFFFF where there is none -- the
+ *             entries, the unreached end points, and the end points with no strict dominator
+ *   out_cut   device, optional, n words, each written. Integer sums: exact, and the same on every run
+ *   result    host, required. All three outputs may be null: the result alone is an answer
+ * The sets are the least fixed point of Avoid(v) = (U over edges p -> v of Avoid(p)) \ {v} with
+ * Avoid(e) = all \ {e} fixed for e in E, where Avoid(v) is the set of k that some walk from E to v
+ * does not contain; Dom(v) is its complement for a reached v. result->rounds counts the rounds r >= 1
+ * of the synchronous iteration Avoid_r+1(v) = Avoid_r(v) | ((U Avoid_r(p)) \ {v}) in which some set
+ * grew, reachedness carried as one more column that is set in the entries' rows: it depends on nothing
+ * but the input.
+ * The padding bits of the input rows are masked, never trusted. Like pg_reach_closure the call reads
+ * no table and triggers no compile, and it never touches the hit counters or their snapshots; ctx only
+ * names the device and its launch knobs ("blocks_per_cu"). It enqueues on hip_stream -- the edges
+ * transposed into scratch, one launch per round, the finish -- and synchronises that stream after
+ * every round, because the host reads the running count back to see whether anything grew, and at
+ * the end. On any input the call ends and stays inside its arrays. n == 0: PG_OK, *result zeroed,
+ * nothing else written (the matrix may then be null). n_entry == 0 or an all-zero svc_select is valid:
+ * nothing, or only E, is reached. PG_EINVAL (pg_last_error names the argument, and for a bad id its
+ * index): a null spec or result; a null matrix with n > 0; a null entry with n_entry > 0; n or n_entry
+ * above 2^15; n_svc 0 or above 4096; an entry id >= n. PG_ENOMEM: the scratch allocation (four n x n
+ * bit matrices and a few words per end point) failed. */
+typedef struct pg_reach_dominators_spec {
+    const uint32_t* matrix;     /* device: n_svc * n rows of pg_reach_row_words(n) words; 4-B aligned, nothing more assumed */
+    uint32_t n;                 /* end points, 0 .. 2^15 */
+    uint32_t n_svc;             /* 1 .. 4096 */
+    const uint8_t* svc_select;  /* host, optional, as in pg_reach_closure_spec */
+    const uint32_t* entry;      /* host, n_entry ids, each < n; duplicates allowed, any order */
+    uint32_t n_entry;           /* 0 .. 2^15; 0 = nothing is reached */
+} pg_reach_dominators_spec;
+typedef struct pg_reach_dominators_result {   /* host */
+    uint32_t n_reached;   /* entries included */
+    uint32_t n_chokes;    /* end points outside E with cut > 0 */
+    uint32_t top;         /* the least end point outside E with the largest cut; 0xFFFFFFFF when n_chokes == 0 */
+    uint32_t top_cut;     /* its cut, 0 when none */
+    uint32_t depth;       /* max over v of |Dom(v)| - 1: the longest chain of strict dominators */
+    uint32_t rounds;      /* as defined above */
+} pg_reach_dominators_result;
+int pg_reach_dominators(pg_ctx* ctx, const pg_reach_dominators_spec* spec, uint32_t* out_dom, uint16_t* out_idom,
+                        uint32_t* out_cut, pg_reach_dominators_result* result, void* hip_stream);
+/* TESTS ONLY -- never on the audit path: pg_reach_dominators's per-word code and plan (dominators.hpp,
+ * the functions the kernels and the launch call) on the host, round by round; matrix and every output
+ * are host arrays. Does not touch the device. */
+int pg_debug_reach_dominators_host(pg_ctx* ctx, const pg_reach_dominators_spec* spec, uint32_t* out_dom, uint16_t* out_idom,
+                                   uint32_t* out_cut, pg_reach_dominators_result* result);
+/* TESTS ONLY: how a pg_reach_dominators over n end points is cut, from the one function the launch
+ * itself uses (dominators.hpp dom_plan): a round's lane words, tile and grid, the edge / transpose
+ * tiles, the cut tiles and the per-row grid of the finish. Launches nothing. */
+typedef struct pg_reach_dominators_plan {
+    uint32_t lane_words;                         /* adjacent bit-words of a row a lane owns in a round: 1, 2 or 4 */
+    uint32_t tile_rows, tile_cols;               /* cells of the sets one workgroup of a round owns */
+    uint32_t row_tiles, col_tiles, round_grid;   /* round_grid = row_tiles * col_tiles */
+    uint32_t t_rows, t_cols;                     /* cells of the edge matrix one transpose tile covers */
+    uint32_t t_row_tiles, t_col_tiles, t_grid;   /* t_grid = t_row_tiles * t_col_tiles */
+    uint32_t cut_rows, cut_cols;                 /* cells of Dom one cut tile covers */
+    uint32_t cut_row_tiles, cut_col_tiles, cut_grid;
+    uint32_t finish_grid;                        /* the most workgroups the size and idom kernels can need: one per row */
+} pg_reach_dominators_plan;
+int pg_debug_reach_dominators_plan(pg_ctx* ctx, uint32_t n, pg_reach_dominators_plan* plan);
+
 /* ---- observed reachability: a flow log as a reach matrix, on the device -----------------------
  * "Which allowed cells has no flow ever used, and which flows fall on a cell the policy does not
  * allow?" The other audits say what the policy allows; this one folds what the cluster did -- a

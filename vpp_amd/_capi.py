@@ -154,6 +154,23 @@ class pg_reach_zones_plan(C.Structure):
                 ("label_grid", C.c_uint32), ("dag_grid", C.c_uint32)]
 
 
+class pg_reach_dominators_spec(C.Structure):
+    _fields_ = [("matrix", C.c_void_p), ("n", C.c_uint32), ("n_svc", C.c_uint32), ("svc_select", C.c_void_p),
+                ("entry", C.c_void_p), ("n_entry", C.c_uint32)]
+
+
+class pg_reach_dominators_result(C.Structure):
+    _fields_ = [("n_reached", C.c_uint32), ("n_chokes", C.c_uint32), ("top", C.c_uint32), ("top_cut", C.c_uint32),
+                ("depth", C.c_uint32), ("rounds", C.c_uint32)]
+
+
+class pg_reach_dominators_plan(C.Structure):
+    _fields_ = [(name, C.c_uint32) for name in (
+        "lane_words", "tile_rows", "tile_cols", "row_tiles", "col_tiles", "round_grid",
+        "t_rows", "t_cols", "t_row_tiles", "t_col_tiles", "t_grid",
+        "cut_rows", "cut_cols", "cut_row_tiles", "cut_col_tiles", "cut_grid", "finish_grid")]
+
+
 OBS_MATCHED, OBS_NO_SRC, OBS_NO_DST, OBS_NO_SVC = 0, 1, 2, 3
 OBSERVED_ACCUMULATE, OBSERVED_MATCH_SRC_PORT = 1, 2
 
@@ -368,6 +385,11 @@ _SIGS = {
     "pg_debug_reach_zones_host": (C.c_int, [_P, C.POINTER(pg_reach_zones_spec), _P, _P, _P, _P, _P, _P,
                                             C.POINTER(pg_reach_zones_result)]),
     "pg_debug_reach_zones_plan": (C.c_int, [_P, C.c_uint32, C.POINTER(pg_reach_zones_plan)]),
+    "pg_reach_dominators": (C.c_int, [_P, C.POINTER(pg_reach_dominators_spec), _P, _P, _P,
+                                      C.POINTER(pg_reach_dominators_result), _P]),
+    "pg_debug_reach_dominators_host": (C.c_int, [_P, C.POINTER(pg_reach_dominators_spec), _P, _P, _P,
+                                                 C.POINTER(pg_reach_dominators_result)]),
+    "pg_debug_reach_dominators_plan": (C.c_int, [_P, C.c_uint32, C.POINTER(pg_reach_dominators_plan)]),
     "pg_reach_observed": (C.c_int, [_P, C.POINTER(pg_reach_observed_spec), C.POINTER(pg_tuple_soa), C.c_uint64, _P, _P, _P,
                                     C.POINTER(pg_reach_observed_result), _P]),
     "pg_debug_reach_observed_host": (C.c_int, [_P, C.POINTER(pg_reach_observed_spec), C.POINTER(pg_tuple_soa), C.c_uint64,

@@ -1,6 +1,6 @@
 // extern "C" boundary of the reachability audits (include/policygpu.h): the matrix, the rule
-// coverage, the port sweep, the diff, the closure, the groups, the paths, the classes, the zones and
-// the observed matrix, each with the host twin the tests compare its kernels to.
+// coverage, the port sweep, the diff, the closure, the groups, the paths, the classes, the zones, the
+// dominators and the observed matrix, each with the host twin the tests compare its kernels to.
 #include <algorithm>
 #include <numeric>
 
@@ -8,6 +8,7 @@
 #include "classes.hpp"
 #include "closure.hpp"
 #include "diff.hpp"
+#include "dominators.hpp"
 #include "groups.hpp"
 #include "observed.hpp"
 #include "paths.hpp"
@@ -1210,6 +1211,180 @@ int pg_debug_reach_zones_plan(pg_ctx* ctx, uint32_t n, pg_reach_zones_plan* plan
     if (n > kClosureMaxN) return fail(ctx, PG_EINVAL, "more than 2^15 end points");
     const ZonesPlan p = zones_plan(n);
     *plan = pg_reach_zones_plan{p.tile_rows, p.tile_cols, p.row_tiles, p.col_tiles, p.bits_grid, p.label_rows, p.label_grid, p.dag_grid};
+    return PG_OK;
+}
+
+}  // extern "C"
+
+// ---- reachability dominators (dominators.hpp) ----------------------------------------------------
+namespace {
+static_assert(sizeof(pg_reach_dominators_result) == sizeof(DomResult), "pg_reach_dominators_result is dominators.hpp's DomResult");
+static_assert(sizeof(pg_reach_dominators_plan) == sizeof(DomPlan), "pg_reach_dominators_plan is dominators.hpp's DomPlan");
+
+// argument checks shared by pg_reach_dominators and its host twin: PG_OK with *empty set when there
+// is no end point (then *result is zeroed here), else *list = the selected slices
+int dominators_args(pg_ctx* ctx, const pg_reach_dominators_spec* spec, pg_reach_dominators_result* result, bool* empty,
+                    std::vector<uint32_t>* list) {
+    if (!ctx) return PG_EINVAL;
+    if (!spec || !result) return fail(ctx, PG_EINVAL, "null spec or result");
+    if (spec->n > kDomMaxN) return fail(ctx, PG_EINVAL, "n: more than 2^15 end points");
+    if (spec->n_entry > kDomMaxEntry) return fail(ctx, PG_EINVAL, "n_entry: more than 2^15 entries");
+    if (!spec->n_svc || spec->n_svc > kDomMaxSvc) return fail(ctx, PG_EINVAL, "n_svc is 0 or above 4096");
+    if (spec->n_entry && !spec->entry) return fail(ctx, PG_EINVAL, "null entry with n_entry > 0");
+    *empty = !spec->n;
+    if (!*empty && !spec->matrix) return fail(ctx, PG_EINVAL, "null matrix");
+    for (uint32_t k = 0; k < spec->n_entry; k++)
+        if (spec->entry[k] >= spec->n)
+            return fail(ctx, PG_EINVAL, "entry[" + std::to_string(k) + "] = " + std::to_string(spec->entry[k]) + " is not below n");
+    if (*empty) *result = pg_reach_dominators_result{0, 0, 0, 0, 0, 0};
+    for (uint32_t v = 0; v < spec->n_svc; v++)
+        if (!spec->svc_select || spec->svc_select[v]) list->push_back(v);
+    return PG_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int pg_reach_dominators(pg_ctx* ctx, const pg_reach_dominators_spec* spec, uint32_t* out_dom, uint16_t* out_idom,
+                        uint32_t* out_cut, pg_reach_dominators_result* result, void* stream) {
+    GUARD_BEGIN
+    bool empty = false;
+    std::vector<uint32_t> list;
+    if (int rc = dominators_args(ctx, spec, result, &empty, &list)) return rc;
+    if (empty) return PG_OK;
+    DEVICE_GUARD(ctx);
+    const DomSpecDev sd{spec->matrix, spec->n, spec->n_svc, list.data(), (uint32_t)list.size(), spec->entry, spec->n_entry};
+    std::string err;
+    DomResult r{0, 0, kDomNone, 0, 0, 0};
+    const int rc = dev_reach_dominators(ctx->eng.tune.blocks_per_cu, sd, out_dom, out_idom, out_cut, &r, stream, &err);
+    if (rc != 0) return fail(ctx, rc == -2 ? PG_ENOMEM : PG_EIO, err);
+    *result = pg_reach_dominators_result{r.n_reached, r.n_chokes, r.top, r.top_cut, r.depth, r.rounds};
+    return PG_OK;
+    GUARD_END(ctx)
+}
+
+int pg_debug_reach_dominators_host(pg_ctx* ctx, const pg_reach_dominators_spec* spec, uint32_t* out_dom, uint16_t* out_idom,
+                                   uint32_t* out_cut, pg_reach_dominators_result* result) {
+    GUARD_BEGIN
+    bool empty = false;
+    std::vector<uint32_t> list;
+    if (int rc = dominators_args(ctx, spec, result, &empty, &list)) return rc;
+    if (empty) return PG_OK;
+    const uint32_t n = spec->n, se = closure_stride(n), sa = dom_stride(n), bw = closure_bit_words(n), rw = (uint32_t)reach_row_words(n);
+    const DomPlan plan = dom_plan(n);
+    // every tile in order, as k_dom_edges_t runs it: the tile's words into `sh`, then per word column
+    // the ballots of the two 64-row halves, lane by lane; the OR of 16 adjacent ET rows is the tile word
+    std::vector<uint32_t> ET((size_t)n * se, 0xA5A5A5A5u), TE((size_t)plan.row_tiles * se, 0u);  // (every word of ET is written below)
+    std::vector<uint32_t> sh((size_t)kDomTRows * kDomTPitch);
+    for (uint32_t it = 0; it < plan.t_grid; it++) {
+        const uint32_t tr = it / plan.t_col_tiles, tc = it % plan.t_col_tiles, r0 = tr * kDomTRows, w0 = tc * kDomTWords;
+        for (uint32_t r = 0; r < kDomTRows; r++)
+            for (uint32_t wl = 0; wl < kDomTWords; wl++) {
+                const uint32_t i = r0 + r, w = w0 + wl;
+                sh[(size_t)r * kDomTPitch + wl] =
+                    i < n && w < se ? dom_edge_word(spec->matrix, list.data(), (uint32_t)list.size(), n, rw, i, w) : 0u;
+            }
+        for (uint32_t q = 0; q < kDomTWords; q++)
+            for (uint32_t k = 0; k < 32; k++) {
+                uint64_t b[2] = {0, 0};
+                for (uint32_t half = 0; half < 2; half++)
+                    for (uint32_t lane = 0; lane < 64; lane++)
+                        b[half] |= (uint64_t)dom_ballot_bit(sh[(size_t)(64u * half + lane) * kDomTPitch + q], k) << lane;
+                const uint32_t c = 32u * (w0 + q) + k;
+                if (c >= n) continue;
+                const uint32_t x[4] = {(uint32_t)b[0], (uint32_t)(b[0] >> 32), (uint32_t)b[1], (uint32_t)(b[1] >> 32)};
+                for (uint32_t u = 0; u < 4; u++) ET[(size_t)c * se + 4u * tr + u] = x[u], TE[(size_t)(c >> 4) * se + 4u * tr + u] |= x[u];
+            }
+    }
+    // as k_dom_init: the entries' rows, live bits and flags
+    const size_t mat = (size_t)n * sa;
+    std::vector<uint32_t> avoid(mat, 0u), D(mat, 0u), Dn(mat, 0u), live(se, 0u), live_n(se), acc(sa);
+    std::vector<uint8_t> is_entry(n, 0);
+    for (uint32_t k = 0; k < spec->n_entry; k++) {
+        const uint32_t e = spec->entry[k];
+        for (uint32_t w = 0; w < sa; w++) avoid[(size_t)e * sa + w] = D[(size_t)e * sa + w] = dom_entry_word(n, e, w);
+        live[e >> 5] |= 1u << (e & 31u), is_entry[e] = 1;
+    }
+    // one round per pass, as k_dom_round runs it: a tile only where a live row has an edge into it, a
+    // row over the live bits of its ET words
+    uint32_t rounds = 0;
+    for (bool go = spec->n_entry != 0; go;) {
+        uint64_t grown = 0;
+        std::fill(live_n.begin(), live_n.end(), 0u);
+        for (uint32_t t = 0; t < plan.row_tiles; t++) {
+            bool need = false;
+            for (uint32_t c = 0; c < bw && !need; c++) need = (TE[(size_t)t * se + c] & live[c]) != 0;
+            if (!need) continue;  // (the workgroup ends having written nothing)
+            for (uint32_t v = t * kDomTileRows; v < std::min(n, (t + 1u) * kDomTileRows); v++) {
+                std::fill(acc.begin(), acc.end(), 0u);
+                for (uint32_t c = 0; c < bw; c++)
+                    for (uint32_t f = ET[(size_t)v * se + c] & live[c]; f; f &= f - 1u) {
+                        const uint32_t* d = &D[(size_t)(32u * c + (uint32_t)__builtin_ctz(f)) * sa];
+                        for (uint32_t w = 0; w < sa; w++) acc[w] |= d[w];
+                    }
+                for (uint32_t w = 0; w < sa; w++) {
+                    uint32_t& a = avoid[(size_t)v * sa + w];
+                    const uint32_t nw = dom_new(acc[w], a, v, w);
+                    a |= nw, Dn[(size_t)v * sa + w] = nw;
+                    if (nw) live_n[v >> 5] |= 1u << (v & 31u);
+                    grown += (uint32_t)__builtin_popcount(nw);
+                }
+            }
+        }
+        go = grown != 0;
+        if (go) rounds++;
+        D.swap(Dn), live.swap(live_n);
+    }
+    // as k_dom_rows: the sizes and the packed rows
+    std::vector<uint32_t> size(n, 0u), cut(n, 0u);
+    for (uint32_t v = 0; v < n; v++) {
+        const uint32_t* row = &avoid[(size_t)v * sa];
+        const bool reached = dom_reached(row, n);
+        for (uint32_t jw = 0; jw < rw; jw++) {
+            const uint32_t w = jw >> 1, h = (dom_word(row[w], reached, n, w) >> (16u * (jw & 1u))) & 0xFFFFu;
+            if (out_dom) out_dom[(size_t)v * rw + jw] = closure_expand(h);
+            size[v] += (uint32_t)__builtin_popcount(h);
+        }
+    }
+    // as k_dom_cut: the column sums of Dom without its diagonal
+    for (uint32_t v = 0; v < n; v++) {
+        const uint32_t* row = &avoid[(size_t)v * sa];
+        for (uint32_t w = 0; w < bw; w++)
+            for (uint32_t d = dom_word(row[w], dom_reached(row, n), n, w) & ~dom_self(v, w); d; d &= d - 1u)
+                cut[32u * w + (uint32_t)__builtin_ctz(d)]++;
+    }
+    if (out_cut) std::copy(cut.begin(), cut.end(), out_cut);
+    // as k_dom_idom
+    for (uint32_t v = 0; out_idom && v < n; v++) {
+        uint32_t found = kDomNoIdom;
+        const uint32_t* row = &avoid[(size_t)v * sa];
+        if (size[v] > 1u)
+            for (uint32_t w = 0; w < bw; w++)
+                for (uint32_t d = dom_word(row[w], true, n, w) & ~dom_self(v, w); d; d &= d - 1u) {
+                    const uint32_t k = 32u * w + (uint32_t)__builtin_ctz(d);
+                    if (dom_is_idom(size[k], size[v])) found = std::min(found, k);
+                }
+        out_idom[v] = (uint16_t)found;
+    }
+    // as k_dom_result
+    uint32_t reached = 0, chokes = 0, largest = 0;
+    uint64_t key = 0;
+    for (uint32_t v = 0; v < n; v++) {
+        reached += size[v] != 0u, largest = std::max(largest, size[v]);
+        if (cut[v] && !is_entry[v]) chokes++, key = std::max(key, dom_top_key(cut[v], v));
+    }
+    *result = pg_reach_dominators_result{reached, chokes, dom_top_of(key), (uint32_t)(key >> 32), largest ? largest - 1u : 0u, rounds};
+    return PG_OK;
+    GUARD_END(ctx)
+}
+
+int pg_debug_reach_dominators_plan(pg_ctx* ctx, uint32_t n, pg_reach_dominators_plan* plan) {
+    if (!ctx || !plan) return PG_EINVAL;
+    if (n > kDomMaxN) return fail(ctx, PG_EINVAL, "n: more than 2^15 end points");
+    const DomPlan p = dom_plan(n);
+    *plan = pg_reach_dominators_plan{p.lane_words, p.tile_rows, p.tile_cols, p.row_tiles, p.col_tiles, p.round_grid,
+                                     p.t_rows, p.t_cols, p.t_row_tiles, p.t_col_tiles, p.t_grid,
+                                     p.cut_rows, p.cut_cols, p.cut_row_tiles, p.cut_col_tiles, p.cut_grid, p.finish_grid};
     return PG_OK;
 }
 

@@ -583,6 +583,53 @@ def reach_zones(engine, closure, n, reps=False, sizes=False, counts=False, dag=F
     return zone, cut(rep), cut(size), cut(out), cut(by), graph, zones_result(res)
 
 
+# ---- reachability dominators (include/policygpu.h pg_reach_dominators) -----------------------
+NO_IDOM = 0xFFFF
+
+
+def dominators_spec(matrix_ptr, n, n_svc, entry, svc_select=None):
+    """pg_reach_dominators_spec -> (spec, the arrays it points into: keep them alive for the call)"""
+    sel = None
+    if svc_select is not None:
+        sel = np.ascontiguousarray(np.asarray(svc_select) != 0, dtype=np.uint8)
+        if sel.shape != (n_svc,):
+            raise ValueError("svc_select takes one entry per slice")
+    ent = np.ascontiguousarray(entry, dtype=np.uint32).reshape(-1)
+    spec = _capi.pg_reach_dominators_spec(matrix_ptr, int(n), int(n_svc), sel.ctypes.data if sel is not None else None,
+                                          ent.ctypes.data if len(ent) else None, len(ent))
+    return spec, (sel, ent)
+
+
+def dominators_result(res):
+    return {"n_reached": res.n_reached, "n_chokes": res.n_chokes, "top": res.top, "top_cut": res.top_cut,
+            "depth": res.depth, "rounds": res.rounds}
+
+
+def reach_dominators(engine, matrix, n, n_svc, entry, svc_select=None, dom=False, idom=False, cut=False, stream=None):
+    """The end points every walk from the entry set must cross, over the ALLOW graph of a square
+    reach_matrix result, on the GPU (pg_reach_dominators). ``matrix`` is an int32 device tensor [n_svc, n,
+    row_words(n)] taken with one end-point list on both sides; ``entry`` the ids of the foothold
+    (duplicates allowed); ``svc_select`` (one flag per slice, None = all) says which slices contribute
+    edges. -> (dom, idom, cut, result): with ``dom`` the dominator sets as an int32 tensor [n,
+    row_words(n)] in the audits' layout (cell (v, k) ALLOW = k dominates v; unpack_closure, reach_diff,
+    reach_groups), with ``idom`` the immediate dominators as an int16 tensor [n] (view it as uint16:
+    NO_IDOM where there is none), with ``cut`` the end points lost with each end point as an int32
+    tensor [n], and {n_reached, n_chokes, top, top_cut, depth, rounds}. Whatever was not asked for is
+    None. The call never touches the hit counters."""
+    rw = reach_row_words(n)
+    if matrix.dtype != torch.int32 or not matrix.is_contiguous() or matrix.numel() != n_svc * n * rw:
+        raise ValueError("a contiguous int32 tensor [n_svc, n, row_words(n)] expected")
+    d = torch.empty((n, rw), dtype=torch.int32, device="cuda") if dom else None
+    i = torch.empty(n, dtype=torch.int16, device="cuda") if idom else None
+    c = torch.empty(n, dtype=torch.int32, device="cuda") if cut else None
+    res = _capi.pg_reach_dominators_result()
+    spec, keep = dominators_spec(matrix.data_ptr() if n else None, n, n_svc, entry, svc_select)
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+    engine._ck(lib.pg_reach_dominators(engine.h, C.byref(spec), ptr(d), ptr(i), ptr(c), C.byref(res), _stream_ptr(stream)))
+    del keep
+    return d, i, c, dominators_result(res)
+
+
 # ---- observed reachability (include/policygpu.h pg_reach_observed) ---------------------------
 def observed_spec(src_ips, dst_ips, services, flags=0):
     """pg_reach_observed_spec over host arrays (reach_spec's, and the PG_OBSERVED_* flags) -> (spec,

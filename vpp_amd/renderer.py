@@ -797,6 +797,72 @@ class Engine:
         self._ck(lib.pg_debug_reach_zones_plan(self.h, int(n), C.byref(p)))
         return {name: getattr(p, name) for name, _ in p._fields_}
 
+    def debug_reach_dominators_host(self, matrix, n, entry, svc_select=None, dom=True, idom=True, cut=True):
+        """TESTS ONLY: pg_reach_dominators's per-word code and plan run on the host
+        (pg_debug_reach_dominators_host) over a numpy array of packed words [n_svc, n, row_words(n)]. ->
+        (dom words u32 [n, row_words(n)], idom u16 [n], cut u32 [n], {n_reached, n_chokes, top, top_cut,
+        depth, rounds}), None for what was not asked for; the outputs are pre-filled with 0xFF.."""
+        import numpy as np
+        from . import device as D
+        m = np.ascontiguousarray(matrix, dtype=np.uint32)
+        rw = lib.pg_reach_row_words(n)
+        n_svc = m.size // (n * rw) if n else 1
+        d = np.full((n, rw), 0xFFFFFFFF, np.uint32) if dom else None
+        i = np.full(n, 0xFFFF, np.uint16) if idom else None
+        c = np.full(n, 0xFFFFFFFF, np.uint32) if cut else None
+        res = _capi.pg_reach_dominators_result()
+        p = lambda x: x.ctypes.data_as(C.c_void_p) if x is not None and x.size else None
+        spec, keep = D.dominators_spec(m.ctypes.data if m.size else None, n, n_svc, entry, svc_select)
+        self._ck(lib.pg_debug_reach_dominators_host(self.h, C.byref(spec), p(d), p(i), p(c), C.byref(res)))
+        del keep
+        return d, i, c, D.dominators_result(res)
+
+    def debug_reach_dominators_plan(self, n):
+        """TESTS ONLY: how pg_reach_dominators over n end points is cut (pg_debug_reach_dominators_plan) ->
+        {lane_words, tile_rows, tile_cols, row_tiles, col_tiles, round_grid, t_rows, t_cols, t_row_tiles,
+        t_col_tiles, t_grid, cut_rows, cut_cols, cut_row_tiles, cut_col_tiles, cut_grid, finish_grid}"""
+        p = _capi.pg_reach_dominators_plan()
+        self._ck(lib.pg_debug_reach_dominators_plan(self.h, int(n), C.byref(p)))
+        return {name: getattr(p, name) for name, _ in p._fields_}
+
+    def reachability_dominators(self, pods, services, entry_pods, host=False):
+        """Incident response: the attacker holds ``entry_pods``; which single pod, if quarantined, cuts
+        them off from the most of ``pods``, and which pod stands last before each pod on every route over
+        ``services``? The exact choke points, where reachability_chokepoints counts one shortest path per
+        pair. One pg_reach_matrix over pods x pods and one pg_reach_dominators. -> (chokes, idom,
+        result): the pods outside the foothold whose removal alone cuts the attacker off from at least one
+        other pod, as [(pod, cut), ...] by cut descending (ties in list order); per listed pod its
+        immediate dominator -- the last pod every route to it crosses -- or None for a pod of the foothold,
+        a pod that is not reached and a pod with no choke point before it; and {n_reached, n_chokes, top,
+        top_cut, depth, rounds} with ``top`` as a pod (None when there is no choke point). Every entry pod
+        has to be among ``pods``. Pods and services as in reachability. ``host``: TESTS ONLY, the host
+        twins."""
+        import numpy as np
+        from . import device as D
+        ips = self._pod_ips(pods)
+        n = len(ips)
+        entry = []
+        for e, ip in zip(entry_pods, self._pod_ips(entry_pods)):
+            at = [k for k in range(n) if ips[k] == ip]
+            if not at:
+                raise ValueError("entry pod %s is not among the pods" % (e,))
+            entry += at
+        if n == 0 or not services:
+            # (no edge: the foothold reaches nothing but itself)
+            return [], [None] * n, {"n_reached": len(set(entry)), "n_chokes": 0, "top": None, "top_cut": 0, "depth": 0,
+                                    "rounds": 0}
+        if host:
+            m = self.debug_reach_matrix_host(ips, ips, services, words=False)
+            _, idom, cut, res = self.debug_reach_dominators_host(m, n, entry, dom=False)
+        else:
+            m = D.reach_matrix(self, ips, ips, services)
+            _, idom, cut, res = D.reach_dominators(self, m, n, len(services), entry, idom=True, cut=True)
+            idom, cut = idom.cpu().numpy().view(np.uint16), cut.cpu().numpy().view(np.uint32)
+        held = set(entry)
+        order = sorted((k for k in range(n) if cut[k] and k not in held), key=lambda k: (-int(cut[k]), k))
+        res = dict(res, top=None if res["n_chokes"] == 0 else pods[res["top"]])
+        return ([(pods[k], int(cut[k])) for k in order], [None if k == D.NO_IDOM else pods[int(k)] for k in idom], res)
+
     def reach_observed(self, src_ips, dst_ips, services, batch, **kw):
         """A flow log as a reach matrix on the GPU: device.reach_observed on this engine (which only names
         the device: the call reads no table)."""
