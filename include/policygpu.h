@@ -1018,6 +1018,102 @@ typedef struct pg_reach_dominators_plan {
 } pg_reach_dominators_plan;
 int pg_debug_reach_dominators_plan(pg_ctx* ctx, uint32_t n, pg_reach_dominators_plan* plan);
 
+/* ---- reachability cut: the fewest end points that cut entries from targets, on the device -----
+ * "The attacker holds these pods and wants those pods. What is the smallest set of pods I must
+ * quarantine so that no route is left, and how many independent routes are there today?" -- the
+ * minimum vertex cut between an entry set E and a target set T, which pg_reach_dominators sees only
+ * at size one. The input has pg_reach_dominators' form: a square pg_reach_matrix out_packed on the
+ * device (n_svc slices of n rows of pg_reach_row_words(n) words), an optional svc_select, host lists
+ * of entry and target end points, and max_cut.
+ *   Edge i -> j: some selected slice holds PG_CONN_ALLOW in cell (i, j) -- pg_reach_closure's rule.
+ *   Self edges, edges into members of E and edges out of members of T never matter, and nothing below
+ *   sees them.
+ *   A set C of end points outside E u T separates when no walk leads from a member of E to a member
+ *   of T in the graph without C. The input is inseparable when E n T is not empty or some edge e -> t
+ *   joins them directly; n_direct counts the distinct pairs (e, t) with e == t or an edge e -> t.
+ *   cut_size is the least |C| over separating C. By Menger's theorem it is the largest number of
+ *   E -> T paths that share no end point outside E u T; each has the form e, interior end points
+ *   outside E u T, t.
+ *   Among the minimum cuts exactly one has a retained region Reach(C) -- the end points reachable from
+ *   E without C, E included -- that is contained in that of every other: the near cut, the quarantine
+ *   closest to the attacker. Exactly one minimises the region that can still reach T in the same
+ *   sense: the far cut, closest to the targets. Both are properties of the graph, not of the algorithm.
+ *   In the split graph (v outside E u T becomes v_in -> v_out of capacity 1, edges unbounded), after
+ *   any maximum flow: near = { v : v_in is residual-reachable from the source, v_out is not }, far =
+ *   { v : v_out residual-reaches the sink, v_in does not }.
+ *   max_cut bounds the search: it stops as soon as max_cut + 1 disjoint paths exist. The run is then
+ *   capped, and the paths are the proof that no cut of that size exists.
+ *   out_cut   device, optional, n bytes of PG_CUT_* flags, each written: the two canonical cuts and
+ *             the members of Reach(near) and Reach(far). All zero when the input is inseparable or the
+ *             run is capped
+ *   out_prev, out_next  device, optional, n uint16_t each, each written: the witness paths. For v
+ *             outside E u T on a witness path its predecessor and successor on that path (the
+ *             predecessor may be an entry, the successor a target); 0xFFFF everywhere else. An interior
+ *             end point is on at most one path; a path starts where out_prev[v] is in E and ends where
+ *             out_next[v] is in T. Which maximum set of paths is found is decided by the rules "a level
+ *             is one residual arc, the least parent, the least target": the same bytes on every run
+ *   result    host, required. All three outputs may be null: the result alone is an answer
+ * Shortest augmenting paths, one per search, found level by level over bit sets; after the last
+ * search one search back from the sink and two plain searches with each cut removed. result->levels
+ * counts the levels of all of them, result->reroutes the residual back arcs on all augmenting paths
+ * -- how often a later route displaced an earlier one; both depend on nothing but the input.
+ * The padding bits of the input rows are masked, never trusted. Like pg_reach_closure the call reads
+ * no table and triggers no compile, and it never touches the hit counters or their snapshots; ctx only
+ * names the device and its launch knobs ("blocks_per_cu"). It enqueues on hip_stream and synchronises
+ * that stream after every level, because the host reads the level's status back, and at the end. On
+ * any input the call ends and stays inside its arrays: at most min(n, max_cut + 1) augmentations of
+ * at most 2 n + 2 levels each. n == 0: PG_OK, *result zeroed, nothing else written (the matrix may
+ * then be null). An empty E or T or an all-zero svc_select is valid: separable, cut_size 0. PG_EINVAL
+ * (pg_last_error names the argument, and for a bad id its index): a null spec or result; a null
+ * matrix with n > 0; a null list with a non-zero count; n, n_entry, n_target or max_cut above 2^15;
+ * n_svc 0 or above 4096; an id >= n. PG_ENOMEM: the scratch allocation (two n x n bit matrices and a
+ * few words per end point) failed. */
+#define PG_CUT_NEAR 1u        /* a member of the near cut */
+#define PG_CUT_FAR 2u         /* a member of the far cut */
+#define PG_CUT_NEAR_REACH 4u  /* reachable from E with the near cut removed, E included */
+#define PG_CUT_FAR_REACH 8u   /* reachable from E with the far cut removed, E included */
+typedef struct pg_reach_cut_spec {
+    const uint32_t* matrix;     /* device: n_svc * n rows of pg_reach_row_words(n) words; 4-B aligned, nothing more assumed */
+    uint32_t n;                 /* end points, 0 .. 2^15 */
+    uint32_t n_svc;             /* 1 .. 4096 */
+    const uint8_t* svc_select;  /* host, optional, as in pg_reach_closure_spec */
+    const uint32_t* entry;      /* host, n_entry ids, each < n; duplicates allowed, any order */
+    uint32_t n_entry;           /* 0 .. 2^15 */
+    const uint32_t* target;     /* host, n_target ids, each < n; duplicates allowed, any order */
+    uint32_t n_target;          /* 0 .. 2^15 */
+    uint32_t max_cut;           /* 0 .. 2^15: the largest cut looked for */
+} pg_reach_cut_spec;
+typedef struct pg_reach_cut_result {   /* host */
+    uint32_t separable;   /* 0 when the input is inseparable */
+    uint32_t capped;      /* 1 when max_cut + 1 disjoint paths exist */
+    uint32_t n_direct;    /* as defined above; separable == (n_direct == 0) */
+    uint32_t cut_size;    /* 0xFFFFFFFF when the input is inseparable or the run is capped */
+    uint32_t n_paths;     /* cut_size; max_cut + 1 when capped; 0 when inseparable */
+    uint32_t near_reach;  /* |Reach(near)|, E included; 0 when there is no cut to report */
+    uint32_t far_reach;   /* |Reach(far)|, E included; 0 when there is no cut to report */
+    uint32_t levels;      /* as defined above */
+    uint32_t reroutes;    /* as defined above */
+} pg_reach_cut_result;
+int pg_reach_cut(pg_ctx* ctx, const pg_reach_cut_spec* spec, uint8_t* out_cut, uint16_t* out_prev, uint16_t* out_next,
+                 pg_reach_cut_result* result, void* hip_stream);
+/* TESTS ONLY -- never on the audit path: pg_reach_cut's per-word code and plan (cut.hpp, the functions
+ * the kernels and the launch call) on the host, level by level; matrix and every output are host
+ * arrays. Does not touch the device. */
+int pg_debug_reach_cut_host(pg_ctx* ctx, const pg_reach_cut_spec* spec, uint8_t* out_cut, uint16_t* out_prev, uint16_t* out_next,
+                            pg_reach_cut_result* result);
+/* TESTS ONLY: how a pg_reach_cut over n end points is cut, from the one function the launch itself
+ * uses (cut.hpp cut_plan): a level's lane words, workgroup and grid, the edge / transpose tiles and
+ * the finish. Launches nothing. */
+typedef struct pg_reach_cut_plan {
+    uint32_t lane_words;                         /* adjacent bit-words of a row a lane reads per step: 1, 2 or 4 */
+    uint32_t level_block, group_nodes;           /* threads of a level's workgroup and the end points it owns */
+    uint32_t row_steps, level_grid;              /* steps of 64 * lane_words words that cover a row; workgroups of a level */
+    uint32_t t_rows, t_cols;                     /* cells of the edge matrix one transpose tile covers */
+    uint32_t t_row_tiles, t_col_tiles, t_grid;   /* t_grid = t_row_tiles * t_col_tiles */
+    uint32_t finish_block, finish_grid;          /* the finish: one workgroup */
+} pg_reach_cut_plan;
+int pg_debug_reach_cut_plan(pg_ctx* ctx, uint32_t n, pg_reach_cut_plan* plan);
+
 /* ---- observed reachability: a flow log as a reach matrix, on the device -----------------------
  * "Which allowed cells has no flow ever used, and which flows fall on a cell the policy does not
  * allow?" The other audits say what the policy allows; this one folds what the cluster did -- a

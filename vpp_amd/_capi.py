@@ -171,6 +171,25 @@ class pg_reach_dominators_plan(C.Structure):
         "cut_rows", "cut_cols", "cut_row_tiles", "cut_col_tiles", "cut_grid", "finish_grid")]
 
 
+class pg_reach_cut_spec(C.Structure):
+    _fields_ = [("matrix", C.c_void_p), ("n", C.c_uint32), ("n_svc", C.c_uint32), ("svc_select", C.c_void_p),
+                ("entry", C.c_void_p), ("n_entry", C.c_uint32), ("target", C.c_void_p), ("n_target", C.c_uint32),
+                ("max_cut", C.c_uint32)]
+
+
+class pg_reach_cut_result(C.Structure):
+    _fields_ = [(name, C.c_uint32) for name in (
+        "separable", "capped", "n_direct", "cut_size", "n_paths", "near_reach", "far_reach", "levels", "reroutes")]
+
+
+class pg_reach_cut_plan(C.Structure):
+    _fields_ = [(name, C.c_uint32) for name in (
+        "lane_words", "level_block", "group_nodes", "row_steps", "level_grid",
+        "t_rows", "t_cols", "t_row_tiles", "t_col_tiles", "t_grid", "finish_block", "finish_grid")]
+
+
+CUT_NEAR, CUT_FAR, CUT_NEAR_REACH, CUT_FAR_REACH = 1, 2, 4, 8
+
 OBS_MATCHED, OBS_NO_SRC, OBS_NO_DST, OBS_NO_SVC = 0, 1, 2, 3
 OBSERVED_ACCUMULATE, OBSERVED_MATCH_SRC_PORT = 1, 2
 
@@ -390,6 +409,9 @@ _SIGS = {
     "pg_debug_reach_dominators_host": (C.c_int, [_P, C.POINTER(pg_reach_dominators_spec), _P, _P, _P,
                                                  C.POINTER(pg_reach_dominators_result)]),
     "pg_debug_reach_dominators_plan": (C.c_int, [_P, C.c_uint32, C.POINTER(pg_reach_dominators_plan)]),
+    "pg_reach_cut": (C.c_int, [_P, C.POINTER(pg_reach_cut_spec), _P, _P, _P, C.POINTER(pg_reach_cut_result), _P]),
+    "pg_debug_reach_cut_host": (C.c_int, [_P, C.POINTER(pg_reach_cut_spec), _P, _P, _P, C.POINTER(pg_reach_cut_result)]),
+    "pg_debug_reach_cut_plan": (C.c_int, [_P, C.c_uint32, C.POINTER(pg_reach_cut_plan)]),
     "pg_reach_observed": (C.c_int, [_P, C.POINTER(pg_reach_observed_spec), C.POINTER(pg_tuple_soa), C.c_uint64, _P, _P, _P,
                                     C.POINTER(pg_reach_observed_result), _P]),
     "pg_debug_reach_observed_host": (C.c_int, [_P, C.POINTER(pg_reach_observed_spec), C.POINTER(pg_tuple_soa), C.c_uint64,

@@ -1,12 +1,13 @@
 // extern "C" boundary of the reachability audits (include/policygpu.h): the matrix, the rule
 // coverage, the port sweep, the diff, the closure, the groups, the paths, the classes, the zones, the
-// dominators and the observed matrix, each with the host twin the tests compare its kernels to.
+// dominators, the cut and the observed matrix, each with the host twin the tests compare its kernels to.
 #include <algorithm>
 #include <numeric>
 
 #include "capi_internal.hpp"
 #include "classes.hpp"
 #include "closure.hpp"
+#include "cut.hpp"
 #include "diff.hpp"
 #include "dominators.hpp"
 #include "groups.hpp"
@@ -1272,7 +1273,7 @@ int pg_debug_reach_dominators_host(pg_ctx* ctx, const pg_reach_dominators_spec* 
     if (empty) return PG_OK;
     const uint32_t n = spec->n, se = closure_stride(n), sa = dom_stride(n), bw = closure_bit_words(n), rw = (uint32_t)reach_row_words(n);
     const DomPlan plan = dom_plan(n);
-    // every tile in order, as k_dom_edges_t runs it: the tile's words into `sh`, then per word column
+    // every tile in order, as k_edges_t (edge_tiles.hpp) runs it: the tile's words into `sh`, then per word column
     // the ballots of the two 64-row halves, lane by lane; the OR of 16 adjacent ET rows is the tile word
     std::vector<uint32_t> ET((size_t)n * se, 0xA5A5A5A5u), TE((size_t)plan.row_tiles * se, 0u);  // (every word of ET is written below)
     std::vector<uint32_t> sh((size_t)kDomTRows * kDomTPitch);
@@ -1385,6 +1386,220 @@ int pg_debug_reach_dominators_plan(pg_ctx* ctx, uint32_t n, pg_reach_dominators_
     *plan = pg_reach_dominators_plan{p.lane_words, p.tile_rows, p.tile_cols, p.row_tiles, p.col_tiles, p.round_grid,
                                      p.t_rows, p.t_cols, p.t_row_tiles, p.t_col_tiles, p.t_grid,
                                      p.cut_rows, p.cut_cols, p.cut_row_tiles, p.cut_col_tiles, p.cut_grid, p.finish_grid};
+    return PG_OK;
+}
+
+}  // extern "C"
+
+// ---- reachability cut (cut.hpp) ------------------------------------------------------------------
+namespace {
+static_assert(sizeof(pg_reach_cut_result) == sizeof(CutResult), "pg_reach_cut_result is cut.hpp's CutResult");
+static_assert(sizeof(pg_reach_cut_plan) == sizeof(CutPlan), "pg_reach_cut_plan is cut.hpp's CutPlan");
+static_assert(PG_CUT_NEAR == kCutNear && PG_CUT_FAR == kCutFar && PG_CUT_NEAR_REACH == kCutNearReach && PG_CUT_FAR_REACH == kCutFarReach,
+              "out_cut's flags are cut.hpp's");
+
+// what both sides work on: the selected slices, the distinct entries ascending, and E and T as bit vectors
+struct CutArgs {
+    bool empty = false;
+    std::vector<uint32_t> list, entry, e_bits, t_bits;
+};
+
+int cut_ids(pg_ctx* ctx, const char* name, const uint32_t* ids, uint32_t count, uint32_t n, std::vector<uint32_t>* bits) {
+    for (uint32_t k = 0; k < count; k++) {
+        if (ids[k] >= n)
+            return fail(ctx, PG_EINVAL, std::string(name) + "[" + std::to_string(k) + "] = " + std::to_string(ids[k]) + " is not below n");
+        (*bits)[ids[k] >> 5] |= 1u << (ids[k] & 31u);
+    }
+    return PG_OK;
+}
+
+// argument checks shared by pg_reach_cut and its host twin: PG_OK with a->empty set when there is no
+// end point (then *result is zeroed here)
+int cut_args(pg_ctx* ctx, const pg_reach_cut_spec* spec, pg_reach_cut_result* result, CutArgs* a) {
+    if (!ctx) return PG_EINVAL;
+    if (!spec || !result) return fail(ctx, PG_EINVAL, "null spec or result");
+    if (spec->n > kCutMaxN) return fail(ctx, PG_EINVAL, "n: more than 2^15 end points");
+    if (spec->n_entry > kCutMaxList) return fail(ctx, PG_EINVAL, "n_entry: more than 2^15 entries");
+    if (spec->n_target > kCutMaxList) return fail(ctx, PG_EINVAL, "n_target: more than 2^15 targets");
+    if (spec->max_cut > kCutMaxCut) return fail(ctx, PG_EINVAL, "max_cut is above 2^15");
+    if (!spec->n_svc || spec->n_svc > kCutMaxSvc) return fail(ctx, PG_EINVAL, "n_svc is 0 or above 4096");
+    if (spec->n_entry && !spec->entry) return fail(ctx, PG_EINVAL, "null entry with n_entry > 0");
+    if (spec->n_target && !spec->target) return fail(ctx, PG_EINVAL, "null target with n_target > 0");
+    a->empty = !spec->n;
+    if (!a->empty && !spec->matrix) return fail(ctx, PG_EINVAL, "null matrix");
+    const uint32_t stride = closure_stride(spec->n);
+    a->e_bits.assign(stride, 0u), a->t_bits.assign(stride, 0u);
+    if (int rc = cut_ids(ctx, "entry", spec->entry, spec->n_entry, spec->n, &a->e_bits)) return rc;
+    if (int rc = cut_ids(ctx, "target", spec->target, spec->n_target, spec->n, &a->t_bits)) return rc;
+    if (a->empty) *result = pg_reach_cut_result{0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (uint32_t v = 0; v < spec->n; v++)
+        if (cut_bit(a->e_bits.data(), v)) a->entry.push_back(v);
+    for (uint32_t v = 0; v < spec->n_svc; v++)
+        if (!spec->svc_select || spec->svc_select[v]) a->list.push_back(v);
+    return PG_OK;
+}
+
+// the host's search state: cut.hip's head and tail
+struct CutHostSearch {
+    std::vector<uint32_t> RX, RY, FX, FY, NX, NY;
+};
+// one level as k_cut_level runs it, word by word of the bit vectors -> grew; *target as the kernel's atomic min
+bool cut_host_level(uint32_t n, uint32_t stride, const uint32_t* M, const uint16_t* link, bool plain, CutHostSearch& s, uint16_t* PX,
+                    uint16_t* PY, const uint32_t* stop, uint32_t* target) {
+    const uint32_t bw = closure_bit_words(n);
+    bool grew = false;
+    for (uint32_t g = 0; g < bw; g++) {
+        const uint32_t rx = s.RX[g], ry = s.RY[g];
+        uint32_t nx = 0, ny = 0;
+        for (uint32_t b = 0; b < 32u && 32u * g + b < n; b++) {
+            const uint32_t v = 32u * g + b;
+            const uint16_t link_v = plain ? kCutNone : link[v];
+            bool hx = false, hy = false;
+            uint32_t px = v, py = v;
+            if (!((rx >> b) & 1u)) {
+                if (cut_x_back(link_v, (s.FY[g] >> b) & 1u)) {
+                    hx = true;
+                } else {
+                    const uint32_t* row = M + (size_t)v * stride;
+                    for (uint32_t w = 0; w < bw && !hx; w++)
+                        if (const uint32_t x = cut_scan_word(row[w], s.FY[w], v, w)) px = cut_first(x, w), hx = true;
+                }
+            }
+            if (plain) {
+                hy = hx;
+            } else if (!((ry >> b) & 1u)) {
+                py = cut_y_source(link_v, v);
+                hy = cut_bit(s.FX.data(), py);
+            }
+            if (hx) {
+                nx |= 1u << b;
+                if (PX) PX[v] = (uint16_t)px;
+            }
+            if (hy) {
+                ny |= 1u << b;
+                if (PY) PY[v] = (uint16_t)py;
+            }
+        }
+        s.NX[g] = nx, s.NY[g] = ny, s.RX[g] = rx | nx, s.RY[g] = ry | ny;
+        grew |= (nx | ny) != 0u;
+        if (stop && (nx & stop[g])) *target = std::min(*target, cut_first(nx & stop[g], g));
+    }
+    return grew;
+}
+// as cut.hip's run_search
+uint32_t cut_host_search(uint32_t n, uint32_t stride, const uint32_t* M, const uint16_t* link, bool plain, CutHostSearch& s, uint16_t* PX,
+                         uint16_t* PY, const uint32_t* stop, uint32_t* levels) {
+    s.NX.assign(stride, 0u), s.NY.assign(stride, 0u);
+    for (;;) {
+        uint32_t target = kCutNoTarget;
+        const bool grew = cut_host_level(n, stride, M, link, plain, s, PX, PY, stop, &target);
+        ++*levels;
+        if (target != kCutNoTarget || !grew) return target;
+        s.FX.swap(s.NX), s.FY.swap(s.NY);
+    }
+}
+}  // namespace
+
+extern "C" {
+
+int pg_reach_cut(pg_ctx* ctx, const pg_reach_cut_spec* spec, uint8_t* out_cut, uint16_t* out_prev, uint16_t* out_next,
+                 pg_reach_cut_result* result, void* stream) {
+    GUARD_BEGIN
+    CutArgs a;
+    if (int rc = cut_args(ctx, spec, result, &a)) return rc;
+    if (a.empty) return PG_OK;
+    DEVICE_GUARD(ctx);
+    const CutSpecDev sd{spec->matrix, spec->n, spec->n_svc, a.list.data(), (uint32_t)a.list.size(), a.entry.data(), (uint32_t)a.entry.size(),
+                        a.e_bits.data(), a.t_bits.data(), spec->max_cut};
+    std::string err;
+    CutResult r{};
+    const int rc = dev_reach_cut(ctx->eng.tune.blocks_per_cu, sd, out_cut, out_prev, out_next, &r, stream, &err);
+    if (rc != 0) return fail(ctx, rc == -2 ? PG_ENOMEM : PG_EIO, err);
+    *result = pg_reach_cut_result{r.separable, r.capped, r.n_direct, r.cut_size, r.n_paths, r.near_reach, r.far_reach, r.levels, r.reroutes};
+    return PG_OK;
+    GUARD_END(ctx)
+}
+
+int pg_debug_reach_cut_host(pg_ctx* ctx, const pg_reach_cut_spec* spec, uint8_t* out_cut, uint16_t* out_prev, uint16_t* out_next,
+                            pg_reach_cut_result* result) {
+    GUARD_BEGIN
+    CutArgs a;
+    if (int rc = cut_args(ctx, spec, result, &a)) return rc;
+    if (a.empty) return PG_OK;
+    const uint32_t n = spec->n, stride = closure_stride(n), bw = closure_bit_words(n), rw = (uint32_t)reach_row_words(n);
+    const uint32_t *e_bits = a.e_bits.data(), *t_bits = a.t_bits.data();
+    // as k_edges_t leaves them: A from dom_edge_word, AT its transpose, padding zero
+    std::vector<uint32_t> A((size_t)n * stride, 0u), AT((size_t)n * stride, 0u);
+    for (uint32_t i = 0; i < n; i++)
+        for (uint32_t w = 0; w < bw; w++) {
+            const uint32_t x = dom_edge_word(spec->matrix, a.list.data(), (uint32_t)a.list.size(), n, rw, i, w);
+            A[(size_t)i * stride + w] = x;
+            for (uint32_t d = x; d; d &= d - 1u) AT[(size_t)(32u * w + (uint32_t)__builtin_ctz(d)) * stride + (i >> 5)] |= 1u << (i & 31u);
+        }
+    std::vector<uint16_t> prev(n, kCutNone), next(n, kCutNone), p_in(n, 0), p_out(n, 0);
+    std::vector<uint8_t> flags(n, 0);
+    CutResult r{};
+    r.cut_size = kCutNoSize;
+    // as k_cut_direct
+    for (uint32_t e : a.entry)
+        for (uint32_t w = 0; w < bw; w++) r.n_direct += (uint32_t)__builtin_popcount(cut_direct_word(A[(size_t)e * stride + w], t_bits[w], e, w));
+    // the heads, as dev_reach_cut makes them
+    CutHostSearch fwd_t, bwd;
+    fwd_t.RX = a.e_bits, fwd_t.FY = a.e_bits, fwd_t.FX.assign(stride, 0u), fwd_t.RY.assign(stride, 0u);
+    bwd.RX = a.t_bits, bwd.FY = a.t_bits, bwd.FX.assign(stride, 0u), bwd.RY.assign(stride, 0u);
+    for (uint32_t w = 0; w < stride; w++) fwd_t.RY[w] = bwd.RY[w] = e_bits[w] | t_bits[w];
+    CutHostSearch fwd = fwd_t;
+    if (!r.n_direct) {
+        r.separable = 1;
+        for (;;) {
+            if (r.n_paths == spec->max_cut + 1u) {
+                r.capped = 1;
+                break;
+            }
+            fwd = fwd_t;
+            const uint32_t target = cut_host_search(n, stride, AT.data(), next.data(), false, fwd, p_in.data(), p_out.data(), t_bits, &r.levels);
+            if (target == kCutNoTarget) break;
+            r.reroutes += cut_augment(target, p_in.data(), p_out.data(), e_bits, t_bits, prev.data(), next.data(), 2u * n + 2u);
+            r.n_paths++;
+        }
+    }
+    if (r.separable && !r.capped) {
+        cut_host_search(n, stride, A.data(), prev.data(), false, bwd, nullptr, nullptr, nullptr, &r.levels);
+        // as k_cut_sets
+        std::vector<uint32_t> near(stride), far(stride);
+        CutHostSearch rn, rf;
+        rn.RX.resize(stride), rf.RX.resize(stride);
+        for (uint32_t w = 0; w < stride; w++) {
+            near[w] = cut_near_word(fwd.RX[w], fwd.RY[w], e_bits[w], t_bits[w]);
+            far[w] = cut_far_word(bwd.RX[w], bwd.RY[w], e_bits[w], t_bits[w]);
+            rn.RX[w] = e_bits[w] | near[w], rf.RX[w] = e_bits[w] | far[w];
+        }
+        rn.RY = rn.RX, rf.RY = rf.RX, rn.FY = rf.FY = a.e_bits, rn.FX.assign(stride, 0u), rf.FX.assign(stride, 0u);
+        cut_host_search(n, stride, AT.data(), nullptr, true, rn, nullptr, nullptr, nullptr, &r.levels);
+        cut_host_search(n, stride, AT.data(), nullptr, true, rf, nullptr, nullptr, nullptr, &r.levels);
+        // as k_cut_finish
+        for (uint32_t w = 0; w < stride; w++) {
+            const uint32_t x[4] = {near[w], far[w], cut_reach_word(rn.RY[w], near[w]), cut_reach_word(rf.RY[w], far[w])};
+            r.near_reach += (uint32_t)__builtin_popcount(x[2]), r.far_reach += (uint32_t)__builtin_popcount(x[3]);
+            for (uint32_t b = 0; b < 32u && 32u * w + b < n; b++)
+                flags[32u * w + b] = cut_flags((x[0] >> b) & 1u, (x[1] >> b) & 1u, (x[2] >> b) & 1u, (x[3] >> b) & 1u);
+        }
+        r.cut_size = r.n_paths;
+    }
+    if (out_cut) std::copy(flags.begin(), flags.end(), out_cut);
+    if (out_prev) std::copy(prev.begin(), prev.end(), out_prev);
+    if (out_next) std::copy(next.begin(), next.end(), out_next);
+    *result = pg_reach_cut_result{r.separable, r.capped, r.n_direct, r.cut_size, r.n_paths, r.near_reach, r.far_reach, r.levels, r.reroutes};
+    return PG_OK;
+    GUARD_END(ctx)
+}
+
+int pg_debug_reach_cut_plan(pg_ctx* ctx, uint32_t n, pg_reach_cut_plan* plan) {
+    if (!ctx || !plan) return PG_EINVAL;
+    if (n > kCutMaxN) return fail(ctx, PG_EINVAL, "n: more than 2^15 end points");
+    const CutPlan p = cut_plan(n);
+    *plan = pg_reach_cut_plan{p.lane_words, p.level_block, p.group_nodes, p.row_steps, p.level_grid,
+                              p.t_rows, p.t_cols, p.t_row_tiles, p.t_col_tiles, p.t_grid, p.finish_block, p.finish_grid};
     return PG_OK;
 }
 

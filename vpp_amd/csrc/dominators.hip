@@ -5,15 +5,8 @@
 // the OR of its rows, static for the call), Avoid, D and D' (n x dom_stride(n): the sets, this
 // round's increments and the next round's, swapped by the host), and two bit vectors over the end
 // points, live and live' (is the row's D non-empty).
-//  k_dom_edges_t  the tiles (128 rows x 32 bit-words of the edge matrix) cut into one contiguous run per
-//                 workgroup, the grid the resident workgroups. A lane makes one bit-word from the selected
-//                 slices (dom_edge_word; the slice list is read through scalar loads) into LDS; then a
-//                 wave takes two bit-word columns of the tile at a time: its lanes read one word of 64
-//                 consecutive rows each from LDS (pitch 33: no bank conflict), one wave-wide ballot per
-//                 column gives 64 rows of that column, and lane k keeps the ballots of its column for
-//                 both halves of the tile: four adjacent ET words, one aligned 16-B store. An OR over
-//                 each 16 lanes (four shuffles) gives the same four words of TE. Every word of ET and
-//                 TE is written, padding zero. No lane reads down a column.
+//  k_edges_t      edge_tiles.hpp, shared with cut.hip: the edge matrix of the selected slices, transposed
+//                 through LDS ballots into ET, and the OR of every 16 rows of ET into TE.
 //  k_dom_init     a workgroup per entry: its Avoid and D rows (dom_entry_word), its live bit and its
 //                 entry flag; duplicates store the same values.
 //  k_dom_round    one round. A workgroup of 16 waves owns 16 rows x 64 * LW bit-words of Avoid; wave w
@@ -50,6 +43,7 @@
 
 #include "audit_launch.hpp"
 #include "dominators.hpp"
+#include "edge_tiles.hpp"
 
 namespace pg {
 
@@ -99,54 +93,7 @@ __device__ __forceinline__ void store_words(uint32_t* p, const uint32_t (&v)[LW]
     else *p = v[0];
 }
 
-struct DomTiles {
-    uint32_t col_tiles, items, per;  // all tiles; those of one workgroup
-};
-
-__global__ __launch_bounds__(kDomBlock) void k_dom_edges_t(const uint32_t* __restrict__ matrix,
-                                                           const uint32_t* __restrict__ svc_list, uint32_t n_list, uint32_t n,
-                                                           uint32_t rw, uint32_t stride, DomTiles S, uint32_t* __restrict__ ET,
-                                                           uint32_t* __restrict__ TE) {
-    __shared__ uint32_t sh[kDomTRows][kDomTPitch];
-    const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t wl = threadIdx.x % kDomTWords, ph = threadIdx.x / kDomTWords;
-    const uint32_t it0 = blockIdx.x * S.per, it1 = min(it0 + S.per, S.items);
-    for (uint32_t it = it0; it < it1; it++) {
-        const uint32_t tr = it / S.col_tiles, tc = it - tr * S.col_tiles;
-        const uint32_t r0 = tr * kDomTRows, w0 = tc * kDomTWords;
-        __syncthreads();  // (every wave has left the tile before)
-        const uint32_t w = w0 + wl;
-        for (uint32_t r = ph; r < kDomTRows; r += kDomBlock / kDomTWords) {
-            const uint32_t i = r0 + r;
-            sh[r][wl] = i < n && w < stride ? dom_edge_word(matrix, svc_list, n_list, n, rw, i, w) : 0u;
-        }
-        __syncthreads();
-        // words q and q + 1 of the tile: lanes 0..31 end with the columns of q, lanes 32..63 with those of q + 1
-        for (uint32_t q = 2u * wave; q < kDomTWords; q += 2u * kDomBlockWaves) {
-            uint32_t v0 = 0, v1 = 0, v2 = 0, v3 = 0;
-#pragma unroll
-            for (uint32_t s = 0; s < 2; s++) {
-                const uint32_t x0 = sh[lane][q + s], x1 = sh[64u + lane][q + s];
-#pragma unroll
-                for (uint32_t k = 0; k < 32; k++) {
-                    const unsigned long long b0 = __ballot(dom_ballot_bit(x0, k)), b1 = __ballot(dom_ballot_bit(x1, k));
-                    if (lane == 32u * s + k) v0 = (uint32_t)b0, v1 = (uint32_t)(b0 >> 32), v2 = (uint32_t)b1, v3 = (uint32_t)(b1 >> 32);
-                }
-            }
-            // (a column at or past n has no cell: its words are zero. stride is a multiple of 4 and the tile's
-            // rows are words 4 tr .. 4 tr + 3 of an ET row: inside it, 16-B aligned)
-            const uint32_t c = 32u * (w0 + q) + lane;
-            if (c < n) *reinterpret_cast<uint4*>(ET + c * stride + 4u * tr) = make_uint4(v0, v1, v2, v3);
-            // the OR of 16 adjacent ET rows: the tile word of the rounds
-#pragma unroll
-            for (int d = 1; d < 16; d <<= 1) {
-                v0 |= (uint32_t)__shfl_xor((int)v0, d, 64), v1 |= (uint32_t)__shfl_xor((int)v1, d, 64);
-                v2 |= (uint32_t)__shfl_xor((int)v2, d, 64), v3 |= (uint32_t)__shfl_xor((int)v3, d, 64);
-            }
-            if ((lane & 15u) == 0 && c < n) *reinterpret_cast<uint4*>(TE + (c >> 4) * stride + 4u * tr) = make_uint4(v0, v1, v2, v3);
-        }
-    }
-}
+using DomTiles = EdgeTiles;  // all tiles; those of one workgroup
 
 __global__ __launch_bounds__(kDomBlock) void k_dom_init(const uint32_t* __restrict__ entry, uint32_t n, uint32_t stride_a,
                                                         uint32_t* __restrict__ avoid, uint32_t* __restrict__ D,
@@ -468,10 +415,10 @@ int dev_reach_dominators(uint32_t blocks_per_cu, const DomSpecDev& spec, uint32_
     if (!h.empty()) HIPCHK(hipMemcpyAsync(list, h.data(), h.size(), hipMemcpyHostToDevice, st));
 
     DomTiles S{p.t_col_tiles, p.t_grid, 0};
-    Runs runs = run_grid(k_dom_edges_t, (int)kDomBlock, 0, S.items, blocks_per_cu);
+    Runs runs = run_grid(k_edges_t<false, true>, (int)kDomBlock, 0, S.items, blocks_per_cu);
     S.per = (uint32_t)runs.per;
-    hipLaunchKernelGGL(k_dom_edges_t, dim3((uint32_t)runs.groups), dim3(kDomBlock), 0, st, spec.matrix, list, spec.n_list, n, rw,
-                       stride_e, S, ET, TE);
+    hipLaunchKernelGGL((k_edges_t<false, true>), dim3((uint32_t)runs.groups), dim3(kDomBlock), 0, st, spec.matrix, list, spec.n_list,
+                       n, rw, stride_e, S, (uint32_t*)nullptr, ET, TE);
     HIPCHK(hipGetLastError());
     if (spec.n_entry) {
         hipLaunchKernelGGL(k_dom_init, dim3(spec.n_entry), dim3(kDomBlock), 0, st, entry, n, stride_a, avoid, D, live, is_entry);

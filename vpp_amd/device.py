@@ -630,6 +630,69 @@ def reach_dominators(engine, matrix, n, n_svc, entry, svc_select=None, dom=False
     return d, i, c, dominators_result(res)
 
 
+# ---- reachability cut (include/policygpu.h pg_reach_cut) --------------------------------------
+NO_HOP = 0xFFFF
+NO_CUT = 0xFFFFFFFF
+
+
+def cut_spec(matrix_ptr, n, n_svc, entry, target, max_cut=16, svc_select=None):
+    """pg_reach_cut_spec -> (spec, the arrays it points into: keep them alive for the call)"""
+    sel = None
+    if svc_select is not None:
+        sel = np.ascontiguousarray(np.asarray(svc_select) != 0, dtype=np.uint8)
+        if sel.shape != (n_svc,):
+            raise ValueError("svc_select takes one entry per slice")
+    ent = np.ascontiguousarray(entry, dtype=np.uint32).reshape(-1)
+    tgt = np.ascontiguousarray(target, dtype=np.uint32).reshape(-1)
+    spec = _capi.pg_reach_cut_spec(matrix_ptr, int(n), int(n_svc), sel.ctypes.data if sel is not None else None,
+                                   ent.ctypes.data if len(ent) else None, len(ent),
+                                   tgt.ctypes.data if len(tgt) else None, len(tgt), int(max_cut))
+    return spec, (sel, ent, tgt)
+
+
+def cut_result(res):
+    return {name: getattr(res, name) for name, _ in res._fields_}
+
+
+def reach_cut(engine, matrix, n, n_svc, entry, target, max_cut=16, svc_select=None, cut=False, paths=False, stream=None):
+    """The fewest end points outside ``entry`` and ``target`` whose removal leaves no walk from an entry to
+    a target, over the ALLOW graph of a square reach_matrix result, on the GPU (pg_reach_cut). ``matrix`` is
+    an int32 device tensor [n_svc, n, row_words(n)] taken with one end-point list on both sides; ``entry``
+    and ``target`` are ids (duplicates allowed); ``svc_select`` (one flag per slice, None = all) says which
+    slices contribute edges; the search stops at ``max_cut`` + 1 disjoint paths. -> (cut, prev, next,
+    result): with ``cut`` the flags as a uint8 tensor [n] (_capi.CUT_NEAR, CUT_FAR, CUT_NEAR_REACH,
+    CUT_FAR_REACH), with ``paths`` the witness paths as two int16 tensors [n] (view them as uint16: NO_HOP
+    off the paths), and {separable, capped, n_direct, cut_size, n_paths, near_reach, far_reach, levels,
+    reroutes} (cut_size NO_CUT when there is none to report). Whatever was not asked for is None. The call
+    never touches the hit counters."""
+    rw = reach_row_words(n)
+    if matrix.dtype != torch.int32 or not matrix.is_contiguous() or matrix.numel() != n_svc * n * rw:
+        raise ValueError("a contiguous int32 tensor [n_svc, n, row_words(n)] expected")
+    c = torch.empty(n, dtype=torch.uint8, device="cuda") if cut else None
+    pv = torch.empty(n, dtype=torch.int16, device="cuda") if paths else None
+    nx = torch.empty(n, dtype=torch.int16, device="cuda") if paths else None
+    res = _capi.pg_reach_cut_result()
+    spec, keep = cut_spec(matrix.data_ptr() if n else None, n, n_svc, entry, target, max_cut, svc_select)
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+    engine._ck(lib.pg_reach_cut(engine.h, C.byref(spec), ptr(c), ptr(pv), ptr(nx), C.byref(res), _stream_ptr(stream)))
+    del keep
+    return c, pv, nx, cut_result(res)
+
+
+def cut_routes(prev, nxt, entries):
+    """the witness paths of a reach_cut as lists of ids, entry first, target last, by their first interior
+    end point ascending; prev / nxt are uint16 host arrays"""
+    held = set(int(e) for e in entries)
+    routes = []
+    for v in range(len(prev)):
+        if prev[v] != NO_HOP and int(prev[v]) in held:
+            route = [int(prev[v]), v]
+            while nxt[route[-1]] != NO_HOP and len(route) <= len(prev) + 1:
+                route.append(int(nxt[route[-1]]))
+            routes.append(route)
+    return routes
+
+
 # ---- observed reachability (include/policygpu.h pg_reach_observed) ---------------------------
 def observed_spec(src_ips, dst_ips, services, flags=0):
     """pg_reach_observed_spec over host arrays (reach_spec's, and the PG_OBSERVED_* flags) -> (spec,

@@ -863,6 +863,76 @@ class Engine:
         res = dict(res, top=None if res["n_chokes"] == 0 else pods[res["top"]])
         return ([(pods[k], int(cut[k])) for k in order], [None if k == D.NO_IDOM else pods[int(k)] for k in idom], res)
 
+    def debug_reach_cut_host(self, matrix, n, entry, target, max_cut=16, svc_select=None, cut=True, paths=True):
+        """TESTS ONLY: pg_reach_cut's per-word code and plan run on the host (pg_debug_reach_cut_host) over a
+        numpy array of packed words [n_svc, n, row_words(n)]. -> (cut u8 [n], prev u16 [n], next u16 [n],
+        {separable, capped, n_direct, cut_size, n_paths, near_reach, far_reach, levels, reroutes}), None for
+        what was not asked for; the outputs are pre-filled with 0xEE.."""
+        import numpy as np
+        from . import device as D
+        m = np.ascontiguousarray(matrix, dtype=np.uint32)
+        rw = lib.pg_reach_row_words(n)
+        n_svc = m.size // (n * rw) if n else 1
+        c = np.full(n, 0xEE, np.uint8) if cut else None
+        pv = np.full(n, 0xEEEE, np.uint16) if paths else None
+        nx = np.full(n, 0xEEEE, np.uint16) if paths else None
+        res = _capi.pg_reach_cut_result()
+        p = lambda x: x.ctypes.data_as(C.c_void_p) if x is not None and x.size else None
+        spec, keep = D.cut_spec(m.ctypes.data if m.size else None, n, n_svc, entry, target, max_cut, svc_select)
+        self._ck(lib.pg_debug_reach_cut_host(self.h, C.byref(spec), p(c), p(pv), p(nx), C.byref(res)))
+        del keep
+        return c, pv, nx, D.cut_result(res)
+
+    def debug_reach_cut_plan(self, n):
+        """TESTS ONLY: how pg_reach_cut over n end points is cut (pg_debug_reach_cut_plan) -> {lane_words,
+        level_block, group_nodes, row_steps, level_grid, t_rows, t_cols, t_row_tiles, t_col_tiles, t_grid,
+        finish_block, finish_grid}"""
+        p = _capi.pg_reach_cut_plan()
+        self._ck(lib.pg_debug_reach_cut_plan(self.h, int(n), C.byref(p)))
+        return {name: getattr(p, name) for name, _ in p._fields_}
+
+    def reachability_cut(self, pods, services, entry_pods, target_pods, max_cut=16, host=False):
+        """Incident response past the single choke point: the attacker holds ``entry_pods`` and wants
+        ``target_pods``; what is the smallest set of other pods among ``pods`` to quarantine so that no route
+        over ``services`` is left, and how many independent routes are there today? One pg_reach_matrix over
+        pods x pods and one pg_reach_cut. -> (near, far, routes, result): the minimum cut closest to the
+        attacker and the one closest to the targets as lists of pods in list order (both [] when the input
+        is inseparable or the search was capped at ``max_cut`` + 1 routes), the witness routes -- pairwise
+        sharing no pod outside the two sets -- as lists of pods from an entry to a target, and {separable,
+        capped, n_direct, cut_size, n_paths, near_reach, far_reach, levels, reroutes} with cut_size None
+        when there is none to report. Every entry and target pod has to be among ``pods``. Pods and services
+        as in reachability. ``host``: TESTS ONLY, the host twins."""
+        import numpy as np
+        from . import device as D
+        ips = self._pod_ips(pods)
+        n = len(ips)
+
+        def ids(names, what):
+            out = []
+            for e, ip in zip(names, self._pod_ips(names)):
+                at = [k for k in range(n) if ips[k] == ip]
+                if not at:
+                    raise ValueError("%s pod %s is not among the pods" % (what, e))
+                out += at
+            return out
+        entry, target = ids(entry_pods, "entry"), ids(target_pods, "target")
+        if n == 0 or not services:
+            # (no edge: only a pod on both sides joins them)
+            direct = len(set(entry) & set(target))
+            return [], [], [], {"separable": int(not direct), "capped": 0, "n_direct": direct, "cut_size": None if direct else 0,
+                                "n_paths": 0, "near_reach": 0 if direct else len(set(entry)),
+                                "far_reach": 0 if direct else len(set(entry)), "levels": 0, "reroutes": 0}
+        if host:
+            m = self.debug_reach_matrix_host(ips, ips, services, words=False)
+            cut, prev, nxt, res = self.debug_reach_cut_host(m, n, entry, target, max_cut)
+        else:
+            m = D.reach_matrix(self, ips, ips, services)
+            cut, prev, nxt, res = D.reach_cut(self, m, n, len(services), entry, target, max_cut, cut=True, paths=True)
+            cut, prev, nxt = cut.cpu().numpy(), prev.cpu().numpy().view(np.uint16), nxt.cpu().numpy().view(np.uint16)
+        res = dict(res, cut_size=None if res["cut_size"] == D.NO_CUT else res["cut_size"])
+        return ([pods[k] for k in range(n) if cut[k] & _capi.CUT_NEAR], [pods[k] for k in range(n) if cut[k] & _capi.CUT_FAR],
+                [[pods[k] for k in route] for route in D.cut_routes(prev, nxt, entry)], res)
+
     def reach_observed(self, src_ips, dst_ips, services, batch, **kw):
         """A flow log as a reach matrix on the GPU: device.reach_observed on this engine (which only names
         the device: the call reads no table)."""
