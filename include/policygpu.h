@@ -201,7 +201,12 @@ int pg_ctx_device(const pg_ctx* ctx);
  * HBM probes at small shapes; default 163840 = whatever fits), "observed_test_first"
  * (pg_reach_observed: a cell's word is loaded before its atomic OR and the atomic skipped where the
  * bit shows; 0 = always the atomic, 1 = a plain load, 2 = a load that the CU's L1 does not answer;
- * the result does not depend on it; default 1, DESIGN.md has the measurement).
+ * the result does not depend on it; default 1, DESIGN.md has the measurement), "cost_lds_bytes"
+ * (pg_reach_cost: cap of the LDS bytes a workgroup may take for its cost row and the weights beside
+ * its two bit vectors, 0..163840; the weights are dropped from LDS first and read through L2, then
+ * the row, which then lives in global memory under global atomics, 0 = nothing staged; the result
+ * does not depend on it -- for tests that reach all three variants at small shapes; default 163840 =
+ * whatever fits).
  * pg_ctx_set_tuning sets one context's knob; pg_set_tuning sets the process default that
  * contexts created afterwards start from. PG_EINVAL for an unknown key or a value out of range. */
 int pg_ctx_set_tuning(pg_ctx* ctx, const char* key, int value);
@@ -1113,6 +1118,91 @@ typedef struct pg_reach_cut_plan {
     uint32_t finish_block, finish_grid;          /* the finish: one workgroup */
 } pg_reach_cut_plan;
 int pg_debug_reach_cut_plan(pg_ctx* ctx, uint32_t n, pg_reach_cut_plan* plan);
+
+/* ---- reachability cost: the cheapest attack paths under per-pod costs, on the device -----------
+ * "What is the cheapest way from this pod to the database, given how hard each pod is to take, and
+ * which pod do most cheap routes cross?" -- what pg_reach_closure's hops and pg_reach_paths answer
+ * when every pod costs the same. The input has pg_reach_dominators' form: a square pg_reach_matrix
+ * out_packed on the device (n_svc slices of n rows of pg_reach_row_words(n) words), an optional
+ * svc_select, a host list src of n_src source end points (duplicates allowed, any order), a host
+ * array weight of n uint16_t, each in 1..65535 -- what it costs to take that end point -- and max_cost.
+ *   Edge i -> j: some selected slice holds PG_CONN_ALLOW in cell (i, j) -- pg_reach_closure's rule.
+ *   Cell (i, i) is a cell like any other.
+ *   cost(s, v) = the least sum of weight[p_t], t = 1..k, over walks s = p_0 -> .. -> p_k = v of k >= 1
+ *   edges. The source is already held and costs nothing; cost(s, s) is the cheapest cycle through s
+ *   (no implicit self-reach, as in the closure). Cell (s, v) is *reached* when such a walk exists and,
+ *   with max_cost != 0, its cost is <= max_cost. Weights are >= 1, so a cheapest walk never repeats
+ *   an end point and every cost is <= n * 65535 < 2^31.
+ *   base(s, p) = 0 if p == s, else cost(s, p). pred(s, v) = the least p with an edge p -> v, base(s, p)
+ *   defined and base(s, p) + weight[v] == cost(s, v) -- the weighted form of pg_reach_paths' least
+ *   predecessor; one exists for every reached cell.
+ *   The path of (s, v) is v, pred(s, v), pred(s, pred(s, v)), .. and ends at the first predecessor
+ *   equal to s (the start, not the cell (s, s)); costs strictly fall along it, so it ends. len(s, v)
+ *   = its edges; its intermediates are its end points other than the start and v.
+ *   out_cost  device, optional, n_src x n uint32_t: cost, PG_COST_NONE where not reached
+ *   out_pred  device, optional, n_src x n uint16_t: pred, PG_COST_NO_PRED where not reached
+ *   out_len   device, optional, n_src x n uint16_t: len, 0 where not reached
+ *   out_via   device, optional, n uint32_t: out_via[k] = the reached cells (s, v), over all listed
+ *             sources with a duplicate source counted twice, whose path has k among its intermediates
+ *             -- the weighted choke points. Cleared on the stream first; integer sums: exact, and the
+ *             same on every run
+ *   result    host, required. All four outputs may be null: the result alone is an answer
+ * Every entry of every given array is written. Nothing in *result is a round count: the search is
+ * asynchronous inside a workgroup and its rounds are no property of the graph.
+ * With every weight 1 and max_cost 0: out_cost is pg_reach_closure's out_hops on the sources' rows
+ * (0 <-> PG_COST_NONE), out_len == out_cost, out_pred is pg_reach_paths' predecessor (the end point
+ * before v on the path of the query (s, v)), and out_via is pg_reach_paths' out_via over the queries
+ * {(s, v) : s listed, every v}.
+ * One workgroup runs every round of one source's search inside a single launch, the cost row in LDS
+ * where it fits ("cost_lds_bytes"): no launch and no host read per round.
+ * The padding bits of the input rows are masked, never trusted. Like pg_reach_closure the call reads
+ * no table and triggers no compile, and it never touches the hit counters or their snapshots; ctx only
+ * names the device and its launch knobs ("blocks_per_cu", "cost_lds_bytes" -- the result depends on
+ * neither). It enqueues on hip_stream and synchronises that stream, because the result comes back. On
+ * any input the call ends and stays inside its arrays: a search is bounded by n + 1 rounds, a path by
+ * n steps. n == 0 or n_src == 0: PG_OK, *result zeroed, out_via cleared when given and n > 0, nothing
+ * else written (the matrix may be null when n == 0). An all-zero svc_select is valid: nothing is
+ * reached. PG_EINVAL (pg_last_error names the argument, and for a bad id or weight its index): a
+ * null spec or result; a null matrix with n > 0; a null src with n_src > 0 or a null weight with
+ * n > 0; n or n_src above 2^15; n_src * n >= 2^28; n_svc 0 or above 4096; a source id >= n; a weight
+ * of 0. PG_ENOMEM: the scratch allocation (two n x n bit matrices, the lists and a row per
+ * workgroup) failed. */
+#define PG_COST_NONE 0xFFFFFFFFu   /* out_cost of a cell that is not reached */
+#define PG_COST_NO_PRED 0xFFFFu    /* out_pred of a cell that is not reached */
+typedef struct pg_reach_cost_spec {
+    const uint32_t* matrix;     /* device: n_svc * n rows of pg_reach_row_words(n) words; 4-B aligned, nothing more assumed */
+    uint32_t n;                 /* end points, 0 .. 2^15 */
+    uint32_t n_svc;             /* 1 .. 4096 */
+    const uint8_t* svc_select;  /* host, optional, as in pg_reach_closure_spec */
+    const uint32_t* src;        /* host, n_src ids, each < n; duplicates allowed, any order */
+    uint32_t n_src;             /* 0 .. 2^15, n_src * n < 2^28 */
+    const uint16_t* weight;     /* host, n weights, each 1 .. 65535 */
+    uint32_t max_cost;          /* 0 = no bound */
+} pg_reach_cost_spec;
+typedef struct pg_reach_cost_result {   /* host */
+    uint64_t n_reached;   /* reached cells */
+    uint64_t n_via;       /* sum of out_via = sum over the reached cells of (len - 1) */
+    uint32_t max_cost;    /* the largest reported cost; 0 when nothing is reached */
+    uint32_t longest;     /* the largest len */
+} pg_reach_cost_result;
+int pg_reach_cost(pg_ctx* ctx, const pg_reach_cost_spec* spec, uint32_t* out_cost, uint16_t* out_pred, uint16_t* out_len,
+                  uint32_t* out_via, pg_reach_cost_result* result, void* hip_stream);
+/* TESTS ONLY -- never on the audit path: pg_reach_cost's per-word code (cost.hpp, the functions the
+ * kernel calls) on the host, source by source; matrix and every output are host arrays. Does not
+ * touch the device. */
+int pg_debug_reach_cost_host(pg_ctx* ctx, const pg_reach_cost_spec* spec, uint32_t* out_cost, uint16_t* out_pred, uint16_t* out_len,
+                             uint32_t* out_via, pg_reach_cost_result* result);
+/* TESTS ONLY: how a pg_reach_cost over n end points is laid out under the context's "cost_lds_bytes",
+ * from the one function the launch itself uses (cost.hpp cost_plan). Launches nothing. */
+typedef struct pg_reach_cost_plan {
+    uint32_t lane_words;                         /* adjacent bit-words of a row a lane reads per step: 1, 2 or 4 */
+    uint32_t block;                              /* threads of the workgroup that owns one source at a time */
+    uint32_t lds_bytes;                          /* its dynamic LDS: two bit vectors, control words, and what is staged */
+    uint32_t row_in_lds, weights_in_lds;         /* the cost row (n x 4 B) and the weights (n x 2 B): 1 = staged in LDS */
+    uint32_t t_rows, t_cols;                     /* cells of the edge matrix one transpose tile covers */
+    uint32_t t_row_tiles, t_col_tiles, t_grid;   /* t_grid = t_row_tiles * t_col_tiles */
+} pg_reach_cost_plan;
+int pg_debug_reach_cost_plan(pg_ctx* ctx, uint32_t n, pg_reach_cost_plan* plan);
 
 /* ---- observed reachability: a flow log as a reach matrix, on the device -----------------------
  * "Which allowed cells has no flow ever used, and which flows fall on a cell the policy does not

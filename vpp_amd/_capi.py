@@ -190,6 +190,24 @@ class pg_reach_cut_plan(C.Structure):
 
 CUT_NEAR, CUT_FAR, CUT_NEAR_REACH, CUT_FAR_REACH = 1, 2, 4, 8
 
+
+class pg_reach_cost_spec(C.Structure):
+    _fields_ = [("matrix", C.c_void_p), ("n", C.c_uint32), ("n_svc", C.c_uint32), ("svc_select", C.c_void_p),
+                ("src", C.c_void_p), ("n_src", C.c_uint32), ("weight", C.c_void_p), ("max_cost", C.c_uint32)]
+
+
+class pg_reach_cost_result(C.Structure):
+    _fields_ = [("n_reached", C.c_uint64), ("n_via", C.c_uint64), ("max_cost", C.c_uint32), ("longest", C.c_uint32)]
+
+
+class pg_reach_cost_plan(C.Structure):
+    _fields_ = [(name, C.c_uint32) for name in (
+        "lane_words", "block", "lds_bytes", "row_in_lds", "weights_in_lds",
+        "t_rows", "t_cols", "t_row_tiles", "t_col_tiles", "t_grid")]
+
+
+NO_COST, NO_PRED = 0xFFFFFFFF, 0xFFFF   # PG_COST_NONE, PG_COST_NO_PRED
+
 OBS_MATCHED, OBS_NO_SRC, OBS_NO_DST, OBS_NO_SVC = 0, 1, 2, 3
 OBSERVED_ACCUMULATE, OBSERVED_MATCH_SRC_PORT = 1, 2
 
@@ -412,6 +430,9 @@ _SIGS = {
     "pg_reach_cut": (C.c_int, [_P, C.POINTER(pg_reach_cut_spec), _P, _P, _P, C.POINTER(pg_reach_cut_result), _P]),
     "pg_debug_reach_cut_host": (C.c_int, [_P, C.POINTER(pg_reach_cut_spec), _P, _P, _P, C.POINTER(pg_reach_cut_result)]),
     "pg_debug_reach_cut_plan": (C.c_int, [_P, C.c_uint32, C.POINTER(pg_reach_cut_plan)]),
+    "pg_reach_cost": (C.c_int, [_P, C.POINTER(pg_reach_cost_spec), _P, _P, _P, _P, C.POINTER(pg_reach_cost_result), _P]),
+    "pg_debug_reach_cost_host": (C.c_int, [_P, C.POINTER(pg_reach_cost_spec), _P, _P, _P, _P, C.POINTER(pg_reach_cost_result)]),
+    "pg_debug_reach_cost_plan": (C.c_int, [_P, C.c_uint32, C.POINTER(pg_reach_cost_plan)]),
     "pg_reach_observed": (C.c_int, [_P, C.POINTER(pg_reach_observed_spec), C.POINTER(pg_tuple_soa), C.c_uint64, _P, _P, _P,
                                     C.POINTER(pg_reach_observed_result), _P]),
     "pg_debug_reach_observed_host": (C.c_int, [_P, C.POINTER(pg_reach_observed_spec), C.POINTER(pg_tuple_soa), C.c_uint64,

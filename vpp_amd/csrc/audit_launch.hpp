@@ -1,5 +1,5 @@
 // What the audit HIP sources (reach.hip, closure.hip, groups.hip, paths.hip, classes.hip, zones.hip,
-// dominators.hip, cut.hip, observed.hip) share on the host side of a launch, on top of hiputil.hpp: the section layout of a scratch block,
+// dominators.hip, cut.hip, observed.hip, cost.hip) share on the host side of a launch, on top of hiputil.hpp: the section layout of a scratch block,
 // the run grid of a kernel whose workgroups each take one contiguous run of work items, and the
 // opt-in to more than 48 KiB of dynamic LDS. HIP only: no host .cpp file and not device.hip.
 #pragma once

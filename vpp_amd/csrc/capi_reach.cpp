@@ -1,12 +1,13 @@
 // extern "C" boundary of the reachability audits (include/policygpu.h): the matrix, the rule
 // coverage, the port sweep, the diff, the closure, the groups, the paths, the classes, the zones, the
-// dominators, the cut and the observed matrix, each with the host twin the tests compare its kernels to.
+// dominators, the cut, the cost and the observed matrix, each with the host twin the tests compare its kernels to.
 #include <algorithm>
 #include <numeric>
 
 #include "capi_internal.hpp"
 #include "classes.hpp"
 #include "closure.hpp"
+#include "cost.hpp"
 #include "cut.hpp"
 #include "diff.hpp"
 #include "dominators.hpp"
@@ -1600,6 +1601,154 @@ int pg_debug_reach_cut_plan(pg_ctx* ctx, uint32_t n, pg_reach_cut_plan* plan) {
     const CutPlan p = cut_plan(n);
     *plan = pg_reach_cut_plan{p.lane_words, p.level_block, p.group_nodes, p.row_steps, p.level_grid,
                               p.t_rows, p.t_cols, p.t_row_tiles, p.t_col_tiles, p.t_grid, p.finish_block, p.finish_grid};
+    return PG_OK;
+}
+
+}  // extern "C"
+
+// ---- reachability cost (cost.hpp) ----------------------------------------------------------------
+namespace {
+static_assert(sizeof(pg_reach_cost_result) == sizeof(CostResult), "pg_reach_cost_result is cost.hpp's CostResult");
+static_assert(sizeof(pg_reach_cost_plan) == sizeof(CostPlan), "pg_reach_cost_plan is cost.hpp's CostPlan");
+static_assert(PG_COST_NONE == kCostNone && PG_COST_NO_PRED == kCostNoPred, "the not-reached marks are cost.hpp's");
+
+// argument checks shared by pg_reach_cost and its host twin: PG_OK with *empty set when there is no
+// end point or no source (then *result is zeroed here), else *list = the selected slices
+int cost_args(pg_ctx* ctx, const pg_reach_cost_spec* spec, pg_reach_cost_result* result, bool* empty, std::vector<uint32_t>* list) {
+    if (!ctx) return PG_EINVAL;
+    if (!spec || !result) return fail(ctx, PG_EINVAL, "null spec or result");
+    if (spec->n > kCostMaxN) return fail(ctx, PG_EINVAL, "n: more than 2^15 end points");
+    if (spec->n_src > kCostMaxSrc) return fail(ctx, PG_EINVAL, "n_src: more than 2^15 sources");
+    if ((uint64_t)spec->n_src * spec->n >= kCostMaxCells) return fail(ctx, PG_EINVAL, "n_src * n reaches 2^28");
+    if (!spec->n_svc || spec->n_svc > kCostMaxSvc) return fail(ctx, PG_EINVAL, "n_svc is 0 or above 4096");
+    if (spec->n && !spec->matrix) return fail(ctx, PG_EINVAL, "null matrix");
+    if (spec->n_src && !spec->src) return fail(ctx, PG_EINVAL, "null src with n_src > 0");
+    if (spec->n && !spec->weight) return fail(ctx, PG_EINVAL, "null weight with n > 0");
+    for (uint32_t k = 0; k < spec->n_src; k++)
+        if (spec->src[k] >= spec->n)
+            return fail(ctx, PG_EINVAL, "src[" + std::to_string(k) + "] = " + std::to_string(spec->src[k]) + " is not below n");
+    for (uint32_t v = 0; v < spec->n; v++)
+        if (!spec->weight[v]) return fail(ctx, PG_EINVAL, "weight[" + std::to_string(v) + "] is 0");
+    *empty = !spec->n || !spec->n_src;
+    if (*empty) *result = pg_reach_cost_result{0, 0, 0, 0};
+    for (uint32_t v = 0; v < spec->n_svc; v++)
+        if (!spec->svc_select || spec->svc_select[v]) list->push_back(v);
+    return PG_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int pg_reach_cost(pg_ctx* ctx, const pg_reach_cost_spec* spec, uint32_t* out_cost, uint16_t* out_pred, uint16_t* out_len,
+                  uint32_t* out_via, pg_reach_cost_result* result, void* stream) {
+    GUARD_BEGIN
+    bool empty = false;
+    std::vector<uint32_t> list;
+    if (int rc = cost_args(ctx, spec, result, &empty, &list)) return rc;
+    if (empty && !(spec->n && out_via)) return PG_OK;
+    DEVICE_GUARD(ctx);
+    // (without a source the launch layer only clears out_via)
+    const CostSpecDev sd{spec->matrix, spec->n, spec->n_svc, list.data(), (uint32_t)list.size(), spec->src, spec->n_src, spec->weight,
+                         spec->max_cost};
+    const CostKnobs knobs{ctx->eng.tune.blocks_per_cu, ctx->eng.tune.cost_lds_bytes};
+    std::string err;
+    CostResult r{};
+    const int rc = dev_reach_cost(knobs, sd, out_cost, out_pred, out_len, out_via, &r, stream, &err);
+    if (rc != 0) return fail(ctx, rc == -2 ? PG_ENOMEM : PG_EIO, err);
+    *result = pg_reach_cost_result{r.n_reached, r.n_via, r.max_cost, r.longest};
+    return PG_OK;
+    GUARD_END(ctx)
+}
+
+int pg_debug_reach_cost_host(pg_ctx* ctx, const pg_reach_cost_spec* spec, uint32_t* out_cost, uint16_t* out_pred, uint16_t* out_len,
+                             uint32_t* out_via, pg_reach_cost_result* result) {
+    GUARD_BEGIN
+    bool empty = false;
+    std::vector<uint32_t> list;
+    if (int rc = cost_args(ctx, spec, result, &empty, &list)) return rc;
+    const uint32_t n = spec->n;
+    if (out_via) std::fill(out_via, out_via + n, 0u);
+    if (empty) return PG_OK;
+    const uint32_t stride = closure_stride(n), bw = closure_bit_words(n), rw = (uint32_t)reach_row_words(n);
+    const uint16_t* wts = spec->weight;
+    // as k_edges_t leaves them: A from dom_edge_word, ET its transpose, padding zero
+    std::vector<uint32_t> A((size_t)n * stride, 0u), ET((size_t)n * stride, 0u);
+    for (uint32_t i = 0; i < n; i++)
+        for (uint32_t w = 0; w < bw; w++) {
+            const uint32_t x = dom_edge_word(spec->matrix, list.data(), (uint32_t)list.size(), n, rw, i, w);
+            A[(size_t)i * stride + w] = x;
+            for (uint32_t d = x; d; d &= d - 1u) ET[(size_t)cost_first(d, w) * stride + (i >> 5)] |= 1u << (i & 31u);
+        }
+    std::vector<uint32_t> row(n), F(stride), N(stride), held(stride);
+    std::vector<uint16_t> pred(n);
+    CostResult r{};
+    for (uint32_t q = 0; q < spec->n_src; q++) {
+        const uint32_t s = spec->src[q];
+        std::fill(row.begin(), row.end(), kCostNone);
+        for (uint32_t w = 0; w < stride; w++) F[w] = dom_self(s, w), N[w] = 0u;
+        // relax, as k_cost_rows: whole-frontier sweeps, here in ascending order
+        for (uint32_t round = 0; round <= n; round++) {
+            bool fell = false;
+            for (uint32_t fw = 0; fw < bw; fw++)
+                for (uint32_t px = F[fw]; px; px &= px - 1u) {
+                    const uint32_t p = cost_first(px, fw), d = cost_base(row[p], p, s);
+                    const uint32_t* arow = &A[(size_t)p * stride];
+                    for (uint32_t w = 0; w < bw; w++)
+                        for (uint32_t e = arow[w]; e; e &= e - 1u) {
+                            const uint32_t v = cost_first(e, w);
+                            uint32_t nd;
+                            if (!cost_offer(d, wts[v], spec->max_cost, &nd) || nd >= row[v]) continue;
+                            row[v] = nd, N[v >> 5] |= 1u << (v & 31u), fell = true;
+                        }
+                }
+            if (!fell) break;
+            std::fill(F.begin(), F.end(), 0u);
+            std::swap(F, N);
+        }
+        // store
+        std::fill(held.begin(), held.end(), 0u);
+        for (uint32_t v = 0; v < n; v++) {
+            if (out_cost) out_cost[(size_t)q * n + v] = row[v];
+            if (row[v] != kCostNone) r.n_reached++, r.max_cost = std::max(r.max_cost, row[v]);
+            if (cost_held(row[v], v, s)) held[v >> 5] |= 1u << (v & 31u);
+        }
+        // pull
+        for (uint32_t v = 0; v < n; v++) {
+            uint32_t pv = kCostNoPred;
+            const uint32_t* trow = &ET[(size_t)v * stride];
+            for (uint32_t w = 0; row[v] != kCostNone && w < bw && pv == kCostNoPred; w++)
+                for (uint32_t e = trow[w] & held[w]; e && pv == kCostNoPred; e &= e - 1u) {
+                    const uint32_t p = cost_first(e, w);
+                    if (cost_ties(cost_base(row[p], p, s), wts[v], row[v])) pv = p;
+                }
+            pred[v] = (uint16_t)pv;
+        }
+        if (out_pred) std::copy(pred.begin(), pred.end(), out_pred + (size_t)q * n);
+        // walk
+        for (uint32_t v = 0; v < n; v++) {
+            uint32_t len = 0;
+            if (pred[v] != kCostNoPred) {
+                len = cost_walk(
+                    v, s, n, [&](uint32_t u) { return (uint32_t)pred[u]; },
+                    [&](uint32_t k) {
+                        if (out_via) out_via[k]++;
+                    });
+                r.n_via += len - 1u, r.longest = std::max(r.longest, len);
+            }
+            if (out_len) out_len[(size_t)q * n + v] = (uint16_t)len;
+        }
+    }
+    *result = pg_reach_cost_result{r.n_reached, r.n_via, r.max_cost, r.longest};
+    return PG_OK;
+    GUARD_END(ctx)
+}
+
+int pg_debug_reach_cost_plan(pg_ctx* ctx, uint32_t n, pg_reach_cost_plan* plan) {
+    if (!ctx || !plan) return PG_EINVAL;
+    if (n > kCostMaxN) return fail(ctx, PG_EINVAL, "n: more than 2^15 end points");
+    const CostPlan p = cost_plan(n, ctx->eng.tune.cost_lds_bytes);
+    *plan = pg_reach_cost_plan{p.lane_words, p.block, p.lds_bytes, p.row_in_lds, p.weights_in_lds,
+                               p.t_rows, p.t_cols, p.t_row_tiles, p.t_col_tiles, p.t_grid};
     return PG_OK;
 }
 

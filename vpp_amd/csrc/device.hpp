@@ -261,6 +261,7 @@ struct Tuning {
     uint32_t rules_wave_agg = 1;      // pg_reach_rules: equal indices of a wave added with one atomic (0 = one per lane)
     uint32_t observed_lds_bytes = 160u << 10;  // pg_reach_observed: cap of the LDS its address tables take (0 = probed in HBM)
     uint32_t observed_test_first = 1;  // pg_reach_observed: a cell's word loaded before its atomic OR (0 = no, 1 = plainly, 2 = past the L1)
+    uint32_t cost_lds_bytes = 160u << 10;  // pg_reach_cost: cap of the LDS its cost row and weights take (0 = the row in global memory)
 };
 // The launch a SINGLE classify makes of one table: the k_classify STAGE its blob is walked
 // at and the hit-counter LDS histogram (device.hip launch_classify dispatches on it;

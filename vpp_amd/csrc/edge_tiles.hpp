@@ -1,11 +1,11 @@
-// The edge / transpose tiles that dominators.hip and cut.hip share: one kernel that makes the bit-word
+// The edge / transpose tiles that dominators.hip, cut.hip and cost.hip share: one kernel that makes the bit-word
 // edge matrix of a square pg_reach_matrix result (dominators.hpp dom_edge_word) and leaves it
 // transposed, and on request as it is and as the OR of every 16 transposed rows. HIP only.
 //
 //  k_edges_t  the tiles (128 rows x 32 bit-words of the edge matrix) cut into one contiguous run per
 //             workgroup, the grid the resident workgroups. A lane makes one bit-word from the selected
 //             slices (dom_edge_word; the slice list is read through scalar loads) into LDS, and with
-//             WITH_A stores it to A as well; then a wave takes two bit-word columns of the tile at a
+//             WITH_A (cut.hip, cost.hip) stores it to A as well; then a wave takes two bit-word columns of the tile at a
 //             time: its lanes read one word of 64 consecutive rows each from LDS (pitch 33: no bank
 //             conflict), one wave-wide ballot per column gives 64 rows of that column, and lane k keeps
 //             the ballots of its column for both halves of the tile: four adjacent ET words, one

@@ -75,6 +75,7 @@ const Knob kKnobs[] = {
     {"rules_wave_agg", &Tuning::rules_wave_agg, 0, 1, false},
     {"observed_lds_bytes", &Tuning::observed_lds_bytes, 0, 160 << 10, false},
     {"observed_test_first", &Tuning::observed_test_first, 0, 2, false},
+    {"cost_lds_bytes", &Tuning::cost_lds_bytes, 0, 160 << 10, false},
 };
 bool Knob::allowed(int v) const {
     if (field == &Tuning::lc_max_stride) return v == 12 || v == 16 || v == 18;

@@ -693,6 +693,58 @@ def cut_routes(prev, nxt, entries):
     return routes
 
 
+# ---- reachability cost (include/policygpu.h pg_reach_cost) ------------------------------------
+NO_COST = _capi.NO_COST
+NO_PRED = _capi.NO_PRED
+
+
+def cost_spec(matrix_ptr, n, n_svc, src, weight, max_cost=0, svc_select=None):
+    """pg_reach_cost_spec -> (spec, the arrays it points into: keep them alive for the call)"""
+    sel = None
+    if svc_select is not None:
+        sel = np.ascontiguousarray(np.asarray(svc_select) != 0, dtype=np.uint8)
+        if sel.shape != (n_svc,):
+            raise ValueError("svc_select takes one entry per slice")
+    s = np.ascontiguousarray(src, dtype=np.uint32).reshape(-1)
+    w = np.asarray(weight).reshape(-1)
+    if len(w) != n or (len(w) and (w.min() < 0 or w.max() > 0xFFFF)):
+        raise ValueError("one weight of 1..65535 per end point expected")
+    w = np.ascontiguousarray(w, dtype=np.uint16)
+    spec = _capi.pg_reach_cost_spec(matrix_ptr, int(n), int(n_svc), sel.ctypes.data if sel is not None else None,
+                                    s.ctypes.data if len(s) else None, len(s), w.ctypes.data if len(w) else None, int(max_cost))
+    return spec, (sel, s, w)
+
+
+def cost_result(res):
+    return {name: getattr(res, name) for name, _ in res._fields_}
+
+
+def reach_cost(engine, matrix, n, n_svc, src, weight, max_cost=0, svc_select=None, cost=True, pred=False, len=False, via=False,
+               stream=None):
+    """The cheapest walks from the end points ``src`` when taking end point v costs ``weight[v]`` (1..65535;
+    the source is held and costs nothing), over the ALLOW graph of a square reach_matrix result, on the GPU
+    (pg_reach_cost). ``matrix`` is an int32 device tensor [n_svc, n, row_words(n)] taken with one end-point
+    list on both sides; ``src`` are ids (duplicates allowed); ``svc_select`` (one flag per slice, None = all)
+    says which slices contribute edges; with ``max_cost`` != 0 only cells of at most that cost are reached.
+    -> (cost, pred, len, via, result): with ``cost`` the costs as an int32 tensor [n_src, n] (view it as
+    uint32: NO_COST where not reached), with ``pred`` the least predecessors and with ``len`` the edges of
+    the cheapest paths as int16 tensors [n_src, n] (view them as uint16: NO_PRED and 0 where not reached),
+    with ``via`` the cheapest paths that cross each end point as an int32 tensor [n], and {n_reached, n_via,
+    max_cost, longest}. Whatever was not asked for is None. The call never touches the hit counters."""
+    rw = reach_row_words(n)
+    if matrix.dtype != torch.int32 or not matrix.is_contiguous() or matrix.numel() != n_svc * n * rw:
+        raise ValueError("a contiguous int32 tensor [n_svc, n, row_words(n)] expected")
+    spec, keep = cost_spec(matrix.data_ptr() if n else None, n, n_svc, src, weight, max_cost, svc_select)
+    new = lambda dtype: torch.empty((spec.n_src, n), dtype=dtype, device="cuda")
+    c, p, ln = new(torch.int32) if cost else None, new(torch.int16) if pred else None, new(torch.int16) if len else None
+    v = torch.empty(n, dtype=torch.int32, device="cuda") if via else None
+    res = _capi.pg_reach_cost_result()
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+    engine._ck(lib.pg_reach_cost(engine.h, C.byref(spec), ptr(c), ptr(p), ptr(ln), ptr(v), C.byref(res), _stream_ptr(stream)))
+    del keep
+    return c, p, ln, v, cost_result(res)
+
+
 # ---- observed reachability (include/policygpu.h pg_reach_observed) ---------------------------
 def observed_spec(src_ips, dst_ips, services, flags=0):
     """pg_reach_observed_spec over host arrays (reach_spec's, and the PG_OBSERVED_* flags) -> (spec,

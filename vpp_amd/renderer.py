@@ -933,6 +933,80 @@ class Engine:
         return ([pods[k] for k in range(n) if cut[k] & _capi.CUT_NEAR], [pods[k] for k in range(n) if cut[k] & _capi.CUT_FAR],
                 [[pods[k] for k in route] for route in D.cut_routes(prev, nxt, entry)], res)
 
+    def debug_reach_cost_host(self, matrix, n, src, weight, max_cost=0, svc_select=None, cost=True, pred=True, len=True, via=True):
+        """TESTS ONLY: pg_reach_cost's per-word code run on the host (pg_debug_reach_cost_host) over a numpy
+        array of packed words [n_svc, n, row_words(n)]. -> (cost u32 [n_src, n], pred u16 [n_src, n], len u16
+        [n_src, n], via u32 [n], {n_reached, n_via, max_cost, longest}), None for what was not asked for; the
+        outputs are pre-filled with 0xEE.."""
+        import numpy as np
+        from . import device as D
+        m = np.ascontiguousarray(matrix, dtype=np.uint32)
+        rw = lib.pg_reach_row_words(n)
+        n_svc = m.size // (n * rw) if n else 1
+        spec, keep = D.cost_spec(m.ctypes.data if m.size else None, n, n_svc, src, weight, max_cost, svc_select)
+        c = np.full((spec.n_src, n), 0xEEEEEEEE, np.uint32) if cost else None
+        pd = np.full((spec.n_src, n), 0xEEEE, np.uint16) if pred else None
+        ln = np.full((spec.n_src, n), 0xEEEE, np.uint16) if len else None
+        v = np.full(n, 0xEEEEEEEE, np.uint32) if via else None
+        res = _capi.pg_reach_cost_result()
+        p = lambda x: x.ctypes.data_as(C.c_void_p) if x is not None and x.size else None
+        self._ck(lib.pg_debug_reach_cost_host(self.h, C.byref(spec), p(c), p(pd), p(ln), p(v), C.byref(res)))
+        del keep
+        return c, pd, ln, v, D.cost_result(res)
+
+    def debug_reach_cost_plan(self, n):
+        """TESTS ONLY: how pg_reach_cost over n end points is laid out under this engine's "cost_lds_bytes"
+        (pg_debug_reach_cost_plan) -> {lane_words, block, lds_bytes, row_in_lds, weights_in_lds, t_rows,
+        t_cols, t_row_tiles, t_col_tiles, t_grid}"""
+        p = _capi.pg_reach_cost_plan()
+        self._ck(lib.pg_debug_reach_cost_plan(self.h, int(n), C.byref(p)))
+        return {name: getattr(p, name) for name, _ in p._fields_}
+
+    def reachability_cost(self, pods, services, src_pods, weights, max_cost=0, host=False):
+        """Budgeted blast radius: the attacker holds each of ``src_pods`` in turn and taking a pod costs
+        ``weights[pod]`` (a mapping pod -> 1..65535, a pod it does not name costs 1); what is the cheapest
+        route to every pod of ``pods`` over ``services``, and which pods do most cheapest routes cross? With
+        ``max_cost`` != 0 only pods within that budget are reached. One pg_reach_matrix over pods x pods and
+        one pg_reach_cost. -> (routes, chokes, result): per source pod a dict {pod: (cost, [source, .., pod])}
+        of the reached pods (the source itself only when a cycle leads back to it); the pods that are an
+        intermediate of some route as [(pod, routes), ...] by routes descending (ties in list order); and
+        {n_reached, n_via, max_cost, longest}. Every source pod has to be among ``pods``. Pods and services as
+        in reachability. ``host``: TESTS ONLY, the host twins."""
+        import numpy as np
+        from . import device as D
+        ips = self._pod_ips(pods)
+        n = len(ips)
+        src = []
+        for e, ip in zip(src_pods, self._pod_ips(src_pods)):
+            at = [k for k in range(n) if ips[k] == ip]
+            if not at:
+                raise ValueError("source pod %s is not among the pods" % (e,))
+            src.append(at[0])
+        if n == 0 or not services or not src:
+            # (no edge or no source: nothing is reached)
+            return [{} for _ in src], [], {"n_reached": 0, "n_via": 0, "max_cost": 0, "longest": 0}
+        w = [int(weights.get(p, 1)) for p in pods]
+        if host:
+            m = self.debug_reach_matrix_host(ips, ips, services, words=False)
+            cost, pred, _, via, res = self.debug_reach_cost_host(m, n, src, w, max_cost, len=False)
+        else:
+            m = D.reach_matrix(self, ips, ips, services)
+            cost, pred, _, via, res = D.reach_cost(self, m, n, len(services), src, w, max_cost, pred=True, via=True)
+            cost, pred, via = cost.cpu().numpy().view(np.uint32), pred.cpu().numpy().view(np.uint16), via.cpu().numpy().view(np.uint32)
+        routes = []
+        for q, s in enumerate(src):
+            found = {}
+            for v in range(n):
+                if cost[q, v] == D.NO_COST:
+                    continue
+                back = [v]
+                while int(pred[q, back[-1]]) != s and len(back) <= n:
+                    back.append(int(pred[q, back[-1]]))
+                found[pods[v]] = (int(cost[q, v]), [pods[k] for k in [s] + back[::-1]])
+            routes.append(found)
+        order = sorted((k for k in range(n) if via[k]), key=lambda k: (-int(via[k]), k))
+        return routes, [(pods[k], int(via[k])) for k in order], res
+
     def reach_observed(self, src_ips, dst_ips, services, batch, **kw):
         """A flow log as a reach matrix on the GPU: device.reach_observed on this engine (which only names
         the device: the call reads no table)."""
